@@ -3,18 +3,23 @@
 
     python bench.py --gpus N --steps K --warmup W          (N > 1: this process only spawns the N ranks, see launch_ranks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+    python bench.py ... --full                              (+ every side measurement and check listed below)
+    python bench.py ... --dump-outputs DIR                  (+ the last timed step's outputs as DIR/*.npy)
 
 A "step" is one JointBilateralFilter::Process (K0 colour pre-smoothing + K1 joint bilateral filter)
 over one batch of synthetic RGB-D frames that is already resident in HBM, made through the boundary entry
 point a caller uses: ONE kde_jbf_process_batch call per step (the drop-in of JointBilateralFilter::Process,
 JointBilateralFilter.cu:283-290), two HIP events around each step.  The K0 / K1 split that `roofline` reads
 is measured in a second, equally long leg right after (kde_jbf_presmooth_batch + kde_jbf_filter_batch, the
-two launches the boundary call makes, three events per step).  At N=1 the workload is
+two launches the boundary call makes, three events per step; --full only).  At N=1 the workload is
 BASELINE config 2's filter on a batch of 640x480 frames (64 frames per GPU: at N=8 that is config 4,
 512 frames sharded 8 ways; weak scaling, no data-path collective — frames are independent units;
 the only exchange is one broadcast of the parameter block from rank 0).
 
-One JSON line is printed by rank 0; besides the contract fields it carries
+A plain run sets up, wakes the GPU up, runs the W warm-up and the K timed steps, writes --dump-outputs if asked and
+prints the line: the contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step = wall time of the K
+timed steps / K), the run's identity (config, ranks_seen, devices, rccl, replicas_only) and a checksum of the output.
+One JSON line is printed by rank 0; with --full it also carries
   roofline     — the dominant kernel (K1) against the HBM roofline: algorithmic 11 B/pixel
                  (4 B depth read + 3 B packed-BGR guide read + 4 B filtered write) x pixels per launch
                  / its average launch duration, measured with HIP events on the launch stream
@@ -34,7 +39,7 @@ One JSON line is printed by rank 0; besides the contract fields it carries
   cpu_baseline_1t — the same on one thread (SURVEY 8d);
   from_idle    — the same W + K steps measured first, from an idle GPU (no wake-up load): what the fixed W = 5 / K = 20
                  contract gives by itself; `value` is the steady-clock figure measured right after;
-  ranks_seen / devices / rccl / replicas_only — who took part (an all-reduce of 1; rank, pid, arch and PCI address of every
+  ranks_seen / devices / rccl / replicas_only (plain runs too) — who took part (an all-reduce of 1; rank, pid, arch and PCI address of every
                  rank's GPU) and over what: RCCL when it came up on every rank, else the in-process gloo fallback, flagged;
   also         — side legs: at every N the config-5 chain on 64 x 640x480 per GPU through the batched entry points (run by
                  every rank, reduced like the headline); at N = 1 the reference constants, K1's dependence on content at
@@ -103,6 +108,14 @@ def parse():
     ap.add_argument("--no-idle-leg", action="store_true", help="skip the from-idle measurement that precedes the headline (profiling runs)")
     ap.add_argument("--dump-frames", default="",
                     help="write this rank's input frames (all colour frames, then all depth frames, raw) for examples/shard_replay --frames-file")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline too: the from-idle leg, the K0 / K1 split leg and the roofline object, the "
+                         "1080p window-19 and chain side legs, the oracle check of the timed output and the CPU baselines (a plain "
+                         "run sets up, warms up, times the K steps and prints the line)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32): the filtered "
+                         "depth and the K0-smoothed colour image of a fixed, seeded sample of frames (all of them when they fit "
+                         "in 60 MB), and the frame indices of that sample (float64)")
     ap.add_argument("--dry-run", action="store_true",
                     help="everything but the GPU work: launch, process groups, fallback, parameter broadcast, partition, the reductions of "
                          "every leg with stand-in timings (CPU test of the N > 1 path)")
@@ -288,6 +301,34 @@ def make_inputs(synth, torch, first_seed, n, w, h, distinct):
     bgr = np.tile(bgr, (reps, 1, 1, 1))[:n]
     depth = np.tile(depth, (reps, 1, 1))[:n]
     return torch.from_numpy(bgr).cuda(), torch.from_numpy(depth).cuda()
+
+
+DUMP_BYTES = 60_000_000        # --dump-outputs: ceiling of all files together (npy headers aside)
+
+
+def dump_outputs(dirname, out, smooth):
+    """--dump-outputs: what the last timed step handed its caller -- the filtered depth `out` [n,H,W] f32 and the K0-smoothed
+    colour image `smooth` [n,H,W,3] u8 (getSmoothImage_Device) -- as float32 .npy files.  All frames when they fit in
+    DUMP_BYTES, else a fixed, seeded sample of whole frames; a frame too large for that: a seeded sample of its pixels."""
+    import torch
+    n, h, w = out.shape
+    per_frame = 16 * h * w                      # 4 B depth + 3 x 4 B colour
+    k = min(n, DUMP_BYTES // per_frame)
+    rng = np.random.default_rng(0)
+    os.makedirs(dirname, exist_ok=True)
+    if k >= 1:
+        idx = np.arange(n) if k == n else np.sort(rng.choice(n, k, replace=False))
+        sel = torch.from_numpy(idx.astype(np.int64)).to(out.device)
+        arrays = {"filtered_depth": out[sel].cpu().numpy(), "smoothed_bgr": smooth[sel].float().cpu().numpy(),
+                  "frame_index": idx.astype(np.float64)}
+    else:
+        px = np.sort(rng.choice(h * w, DUMP_BYTES // 24, replace=False))      # + 8 B of float64 index per pixel
+        sel = torch.from_numpy(px.astype(np.int64)).to(out.device)
+        arrays = {"filtered_depth": out[0].reshape(-1)[sel].cpu().numpy(), "smoothed_bgr": smooth[0].reshape(-1, 3)[sel].float().cpu().numpy(),
+                  "frame0_pixel_index": px.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, f"{name}.npy"), np.ascontiguousarray(a))
+    return sorted(arrays)
 
 
 def time_steps(torch, jbf, depth, color, smooth, out, steps, warmup, barrier, wakeup_ms=0.0, split=False, keep_busy_ms=0.0):
@@ -504,19 +545,22 @@ def main():
             time.sleep(1.0)
         dt = comm.allreduce_max(1e-3 * (rank + 1))
         checksum = comm.allreduce_sum([float(first), float(count)])
-        # the side legs' reductions on stand-in timings (rank r is r + 1 times slower than rank 0)
-        fake = {"fhd_w19_config3": {"workload": "stand-in", "px": 32 * 1920 * 1080, "steps": 3, "dt_s": 0.03 * (rank + 1),
-                                    "k0_ms": 0.5 * (rank + 1), "k1_ms": 10.0 * (rank + 1)},
-                "vga_chain_batch64": {"frames": 64, "px": 64 * 640 * 480, "batched_ms": 1.7 * (rank + 1)}}
-        legs = reduce_shard_legs(comm.gather_objects(fake), world)
+        # (--full) the side legs' reductions on stand-in timings (rank r is r + 1 times slower than rank 0)
+        legs = None
+        if args.full:
+            fake = {"fhd_w19_config3": {"workload": "stand-in", "px": 32 * 1920 * 1080, "steps": 3, "dt_s": 0.03 * (rank + 1),
+                                        "k0_ms": 0.5 * (rank + 1), "k1_ms": 10.0 * (rank + 1)},
+                    "vga_chain_batch64": {"frames": 64, "px": 64 * 640 * 480, "batched_ms": 1.7 * (rank + 1)}}
+            legs = reduce_shard_legs(comm.gather_objects(fake), world)
         if rank == 0:
-            print(json.dumps({"metric": METRIC, "value": 0.0, "unit": "Mpixels/s", "n_gpus": world, "steps": args.steps,
-                              "warmup": args.warmup, "dry_run": True, "max_dt_over_ranks": dt, "replicas_only": replicas_only,
-                              "scaling": "strong" if strong else "weak", "ranks_seen": ranks_seen, "devices": devices, "rccl": rccl,
-                              "checksum": {"sum_first_frames": checksum[0], "frames": int(checksum[1])},
-                              "roofline": {"fhd_w19": legs["fhd_w19_config3"]}, "also": {"vga_chain_batch64": legs["vga_chain_batch64"]},
-                              "config": {"window": p.window_size, "frames_per_gpu": count, "sharding": sharding_txt}}),
-                  file=real_stdout, flush=True)
+            res = {"metric": METRIC, "value": 0.0, "unit": "Mpixels/s", "n_gpus": world, "steps": args.steps,
+                   "warmup": args.warmup, "dry_run": True, "full": args.full, "max_dt_over_ranks": dt, "replicas_only": replicas_only,
+                   "scaling": "strong" if strong else "weak", "ranks_seen": ranks_seen, "devices": devices, "rccl": rccl,
+                   "checksum": {"sum_first_frames": checksum[0], "frames": int(checksum[1])},
+                   "config": {"window": p.window_size, "frames_per_gpu": count, "sharding": sharding_txt}}
+            if legs is not None:
+                res.update(roofline={"fhd_w19": legs["fhd_w19_config3"]}, also={"vga_chain_batch64": legs["vga_chain_batch64"]})
+            print(json.dumps(res), file=real_stdout, flush=True)
         comm.close()
         return
     if count < 1:
@@ -532,67 +576,46 @@ def main():
     if args.variant >= 0:
         jbf.set_variant(args.variant)
 
-    # from an idle GPU first (the W + K contract by itself), then at the clock the GPU holds under load (the headline)
+    # (--full) from an idle GPU first (the W + K contract by itself), then at the clock the GPU holds under load (the headline)
     idle = None
-    if args.wakeup_ms > 0 and not args.no_idle_leg:
+    if args.full and args.wakeup_ms > 0 and not args.no_idle_leg:
         dt_i, st_i, _, _, _, _ = time_steps(torch, jbf, depth, color, smooth, out, args.steps, args.warmup, barrier, 0.0)
         dt_i = comm.allreduce_max(dt_i)
         idle = {"value": total_frames * W * H * args.steps / dt_i / 1e6, "ms_per_step": dt_i / args.steps * 1e3,
                 "step_gpu_ms_first_median_last": [float(st_i[0]), float(np.median(st_i)), float(st_i[-1])],
                 "note": "same W warm-up + K timed steps started from an idle GPU (lowest clock level), measured before the headline"}
     # ---- the headline: K x kde_jbf_process_batch --------------------------------------------------------------------
-    out2 = torch.empty_like(out)            # (allocated before anything is timed: no allocation gap between the two legs)
+    out2 = torch.empty_like(out) if args.full else None     # (allocated before anything is timed: no allocation gap between the two legs)
     busy = 30.0 if args.wakeup_ms > 0 else 0.0      # --wakeup-ms 0 = the bare W + K contract, as in the from-idle leg
     dt, step_ms, _, _, woke, filler = time_steps(torch, jbf, depth, color, smooth, out, args.steps, args.warmup, barrier, args.wakeup_ms,
                                                  keep_busy_ms=busy)
+    dumped = None
+    if args.dump_outputs and rank == 0:     # what the last timed step handed its caller, before any other leg runs
+        dumped = dump_outputs(args.dump_outputs, out, jbf.getSmoothImage_Device(count).reshape(count, H, W, 3))
     # ---- the same K steps as two separate launches, right behind it, into buffers of their own: the per-kernel times the
     # roofline object reads.  (A short wake-up of its own: the barriers between the legs idle the GPU for a moment) ----
-    dt_s, _, k0_ms, k1_ms, _, _ = time_steps(torch, jbf, depth, color, smooth, out2, args.steps, args.warmup, barrier,
-                                             min(args.wakeup_ms, 50.0), split=True, keep_busy_ms=busy)
-    dt, dt_s = comm.allreduce_max(dt), comm.allreduce_max(dt_s)
-    split_same = bool(torch.equal(out2, out))
-    del out2
-    smooth0 = jbf.getSmoothImage_Device(count)[0].cpu().numpy() if count > 1 else jbf.getSmoothImage_Device().cpu().numpy()
-    out0 = out[0].cpu().numpy()
+    # This leg, the side legs and the checks of the line are --full only: a plain run stops at the headline
+    if args.full:
+        dt_s, _, k0_ms, k1_ms, _, _ = time_steps(torch, jbf, depth, color, smooth, out2, args.steps, args.warmup, barrier,
+                                                 min(args.wakeup_ms, 50.0), split=True, keep_busy_ms=busy)
+        dt_s = comm.allreduce_max(dt_s)
+        split_same = bool(torch.equal(out2, out))
+        del out2
+    dt = comm.allreduce_max(dt)
     checksum = comm.allreduce_sum([float(out.double().sum().item()), float(count)])
-    k1_per_rank = comm.gather_objects(float(np.mean(k1_ms)))
-    # ---- side legs every rank runs on its own GPU (north_star: 640x480 AND 1920x1080 batches at 1/2/4/8 GPUs) --------
     legs = None
-    if not args.no_extra:
-        legs = reduce_shard_legs(comm.gather_objects(shard_legs(torch, filters, synth, args, barrier)), world)
+    if args.full:
+        smooth0 = jbf.getSmoothImage_Device(count)[0].cpu().numpy() if count > 1 else jbf.getSmoothImage_Device().cpu().numpy()
+        out0 = out[0].cpu().numpy()
+        k1_per_rank = comm.gather_objects(float(np.mean(k1_ms)))
+        # ---- side legs every rank runs on its own GPU (north_star: 640x480 AND 1920x1080 batches at 1/2/4/8 GPUs) ----
+        if not args.no_extra:
+            legs = reduce_shard_legs(comm.gather_objects(shard_legs(torch, filters, synth, args, barrier)), world)
 
     if rank == 0:
-        px_per_launch = count * W * H
-        k1_avg_ms = float(np.mean(k1_ms))
+        value = total_frames * W * H * args.steps / dt / 1e6
         names = filters.JointBilateralFilter.variants()
         vname = names[args.variant] if args.variant >= 0 else next((nm for nm in names[1:] if nm.startswith(f"w{p.window_size}-")), None)
-        entry, src = pmc_lookup(args.pmc_json, p.window_size, vname)
-        roof = {"bound": "hbm",
-                "frac_vga_w11": None,       # K1 on this run's batch (64 x 640x480 per GPU, window 11) / 8 TB/s
-                "frac_fhd_w19": None,       # K1 on 32 x 1920x1080 per GPU, window 19: the pass north_star's 70 % target names
-                "limiter": "valu-issue (K1 does 2 exp + ~30 flops per tap against 11 B/pixel; see roofline.valu)",
-                "kernel": "K1 joint_bilateral_filtering",
-                "measured_in": "the split leg: the same W + K steps issued as kde_jbf_presmooth_batch + kde_jbf_filter_batch right after the "
-                               "headline's K boundary calls, HIP events on the launch stream"}
-        roof.update(k1_roofline(px_per_launch, k1_avg_ms, entry, src))
-        if (W, H, p.window_size) == (640, 480, 11):
-            roof["frac_vga_w11"] = roof["frac"]
-        roof["k0_avg_launch_ms"] = float(np.mean(k0_ms))
-        try:        # K0 of the same profiled build: HBM traffic over its 6 B/pixel and its share of the VALU roof (profiles/pmc_bench.json)
-            pj = json.load(open(args.pmc_json))
-            k0e = max((k for k in pj["kernels"] if "presmooth_kernel" in k["kernel"]), key=lambda k: k["grid"]) if entry else None
-            if k0e:
-                roof["k0"] = {"kernel": k0e["kernel"], "avg_launch_ms": roof["k0_avg_launch_ms"], "algorithmic_bytes_per_pixel": 6.0,
-                              "traffic_over_algorithmic": k0e["derived"].get("traffic_ratio"), "valu_ceiling_frac": k0e["derived"].get("valu_cycles_frac"),
-                              "lds_conflict_frac": k0e["derived"].get("lds_conflict_frac"),
-                              "tile_walk": "XCD bands in runs of four adjacent tiles per workgroup (inputs > 32 MiB)"}
-        except Exception:       # noqa: BLE001 -- no profile: the live time stands alone
-            pass
-        roof["launch_ms_first_min_max"] = [float(k1_ms[0]), float(np.min(k1_ms)), float(np.max(k1_ms))]   # clock ramp shows here
-        roof["launch_ms"] = {"mean": k1_avg_ms, "median": float(np.median(k1_ms)), "min": float(np.min(k1_ms)),
-                             "max": float(np.max(k1_ms)), "first": float(k1_ms[0])}
-        roof["k1_avg_launch_ms_per_rank"] = k1_per_rank
-        value = total_frames * W * H * args.steps / dt / 1e6
         res = {
             "metric": METRIC,
             "value": value,
@@ -601,7 +624,7 @@ def main():
             "untimed_steps_enqueued_before_the_start_barrier": filler,
             "ms_per_step": dt / args.steps * 1e3,
             "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
+            "dtype": "f32", "data": "synthetic", "full": args.full,
             "config": {
                 "workload": f"JointBilateralFilter::Process (K0 pre-smooth 5/30/30 + K1) on {total_frames} x {W}x{H} "
                             f"synthetic RGB-D frames ({count} per GPU), window {p.window_size} (radius {p.window_size // 2}), "
@@ -613,35 +636,67 @@ def main():
             },
             "ranks_seen": ranks_seen, "devices": devices, "distinct_devices": len({d.get("pci_bus_id") for d in devices}),
             "rccl": rccl, "replicas_only": replicas_only,
-            "boundary_vs_split": {"step_gpu_ms_mean": float(np.mean(step_ms)), "step_gpu_ms_median": float(np.median(step_ms)),
-                                  "step_gpu_ms_all": [round(float(v), 4) for v in step_ms],
-                                  "split_leg_ms_per_step": dt_s / args.steps * 1e3, "split_leg_value": total_frames * W * H * args.steps / dt_s / 1e6,
-                                  "value_over_split_leg_value": value / (total_frames * W * H * args.steps / dt_s / 1e6),
-                                  "k0_plus_k1_ms": float(np.mean(k0_ms) + np.mean(k1_ms)), "outputs_bit_identical": split_same},
-            "roofline": roof,
             "checksum": {"sum_filtered_mm": checksum[0], "frames": int(checksum[1])},
         }
-        if idle:
-            res["from_idle"] = idle
-        if not args.no_verify:
-            res["verified"] = verify_frame0(args, p, synth, first, out0, smooth0, args.variant)
-        if world == 1 and args.cpu_seconds > 0:
-            res["cpu_baseline"] = cpu_baseline(args, synth, args.cpu_seconds)
-            res["cpu_baseline_1t"] = cpu_baseline(args, synth, max(3.0, args.cpu_seconds / 2), threads=1)
-        if legs is not None:
-            fhd = legs.pop("fhd_w19_config3")
-            names19 = next((nm for nm in names[1:] if nm.startswith("w19-")), None)
-            e19, s19 = pmc_lookup(args.pmc_json, 19, names[args.variant] if args.variant >= 0 else names19)
-            fhd.update(k1_roofline(fhd["px_per_gpu"], fhd["k1_avg_launch_ms"], e19, s19), bound="hbm", limiter="valu-issue")
-            res["roofline"]["fhd_w19"] = fhd
-            res["roofline"]["frac_fhd_w19"] = fhd["frac"]
-            res["also"] = legs
-            if world == 1:
-                res["also"].update(single_gpu_extras(torch, filters, synth, args))
-                floor = res["also"].get("k1_w19_content_dependence", {}).get("synthetic/noelide")
-                if floor:
-                    fhd["k1_mpix_s_noelide"] = floor["k1_mpix_s"]
-                    fhd["k1_ms_noelide"] = floor["k1_ms"]
+        if dumped:
+            res["dumped_outputs"] = {"dir": args.dump_outputs, "files": [f"{nm}.npy" for nm in dumped],
+                                     "of": "the last timed step (rank 0's frames)"}
+        if args.full:
+            px_per_launch = count * W * H
+            k1_avg_ms = float(np.mean(k1_ms))
+            entry, src = pmc_lookup(args.pmc_json, p.window_size, vname)
+            roof = {"bound": "hbm",
+                    "frac_vga_w11": None,       # K1 on this run's batch (64 x 640x480 per GPU, window 11) / 8 TB/s
+                    "frac_fhd_w19": None,       # K1 on 32 x 1920x1080 per GPU, window 19: the pass north_star's 70 % target names
+                    "limiter": "valu-issue (K1 does 2 exp + ~30 flops per tap against 11 B/pixel; see roofline.valu)",
+                    "kernel": "K1 joint_bilateral_filtering",
+                    "measured_in": "the split leg: the same W + K steps issued as kde_jbf_presmooth_batch + kde_jbf_filter_batch right after the "
+                                   "headline's K boundary calls, HIP events on the launch stream"}
+            roof.update(k1_roofline(px_per_launch, k1_avg_ms, entry, src))
+            if (W, H, p.window_size) == (640, 480, 11):
+                roof["frac_vga_w11"] = roof["frac"]
+            roof["k0_avg_launch_ms"] = float(np.mean(k0_ms))
+            try:        # K0 of the same profiled build: HBM traffic over its 6 B/pixel and its share of the VALU roof (profiles/pmc_bench.json)
+                pj = json.load(open(args.pmc_json))
+                k0e = max((k for k in pj["kernels"] if "presmooth_kernel" in k["kernel"]), key=lambda k: k["grid"]) if entry else None
+                if k0e:
+                    roof["k0"] = {"kernel": k0e["kernel"], "avg_launch_ms": roof["k0_avg_launch_ms"], "algorithmic_bytes_per_pixel": 6.0,
+                                  "traffic_over_algorithmic": k0e["derived"].get("traffic_ratio"), "valu_ceiling_frac": k0e["derived"].get("valu_cycles_frac"),
+                                  "lds_conflict_frac": k0e["derived"].get("lds_conflict_frac"),
+                                  "tile_walk": "XCD bands in runs of four adjacent tiles per workgroup (inputs > 32 MiB)"}
+            except Exception:       # noqa: BLE001 -- no profile: the live time stands alone
+                pass
+            roof["launch_ms_first_min_max"] = [float(k1_ms[0]), float(np.min(k1_ms)), float(np.max(k1_ms))]   # clock ramp shows here
+            roof["launch_ms"] = {"mean": k1_avg_ms, "median": float(np.median(k1_ms)), "min": float(np.min(k1_ms)),
+                                 "max": float(np.max(k1_ms)), "first": float(k1_ms[0])}
+            roof["k1_avg_launch_ms_per_rank"] = k1_per_rank
+            res["boundary_vs_split"] = {"step_gpu_ms_mean": float(np.mean(step_ms)), "step_gpu_ms_median": float(np.median(step_ms)),
+                                        "step_gpu_ms_all": [round(float(v), 4) for v in step_ms],
+                                        "split_leg_ms_per_step": dt_s / args.steps * 1e3, "split_leg_value": total_frames * W * H * args.steps / dt_s / 1e6,
+                                        "value_over_split_leg_value": value / (total_frames * W * H * args.steps / dt_s / 1e6),
+                                        "k0_plus_k1_ms": float(np.mean(k0_ms) + np.mean(k1_ms)), "outputs_bit_identical": split_same}
+            res["roofline"] = roof
+            if idle:
+                res["from_idle"] = idle
+            if not args.no_verify:
+                res["verified"] = verify_frame0(args, p, synth, first, out0, smooth0, args.variant)
+            if world == 1 and args.cpu_seconds > 0:
+                res["cpu_baseline"] = cpu_baseline(args, synth, args.cpu_seconds)
+                res["cpu_baseline_1t"] = cpu_baseline(args, synth, max(3.0, args.cpu_seconds / 2), threads=1)
+            if legs is not None:
+                fhd = legs.pop("fhd_w19_config3")
+                names19 = next((nm for nm in names[1:] if nm.startswith("w19-")), None)
+                e19, s19 = pmc_lookup(args.pmc_json, 19, names[args.variant] if args.variant >= 0 else names19)
+                fhd.update(k1_roofline(fhd["px_per_gpu"], fhd["k1_avg_launch_ms"], e19, s19), bound="hbm", limiter="valu-issue")
+                res["roofline"]["fhd_w19"] = fhd
+                res["roofline"]["frac_fhd_w19"] = fhd["frac"]
+                res["also"] = legs
+                if world == 1:
+                    res["also"].update(single_gpu_extras(torch, filters, synth, args))
+                    floor = res["also"].get("k1_w19_content_dependence", {}).get("synthetic/noelide")
+                    if floor:
+                        fhd["k1_mpix_s_noelide"] = floor["k1_mpix_s"]
+                        fhd["k1_ms_noelide"] = floor["k1_ms"]
         print(json.dumps(res), file=real_stdout, flush=True)
     barrier()           # the other ranks stay until rank 0 has checked and printed
     comm.close()

@@ -21,7 +21,7 @@ def _run(extra, env=None, timeout=240):
 
 @pytest.mark.parametrize("n", [1, 2, 4, 8])
 def test_plain_command_launches_n_ranks(n):
-    r = _run(["--gpus", str(n), "--dry-run", "--steps", "2", "--warmup", "1"])
+    r = _run(["--gpus", str(n), "--dry-run", "--steps", "2", "--warmup", "1", "--full"])
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout                                    # ONE JSON line, from rank 0
@@ -41,11 +41,19 @@ def test_plain_command_launches_n_ranks(n):
     assert j["rccl"]["error"] is None and "REPLICAS ONLY" not in j["config"]["sharding"]
 
 
+@pytest.mark.parametrize("n", [1, 2])
+def test_a_plain_run_leaves_the_side_legs_to_full(n):
+    """without --full the line carries the headline, the run's identity and the checksum, and no side leg"""
+    j = json.loads([ln for ln in _run(["--gpus", str(n), "--dry-run", "--steps", "3", "--warmup", "1"]).stdout.splitlines() if ln.strip()][0])
+    assert j["full"] is False and j["steps"] == 3 and j["ranks_seen"] == n and j["checksum"]["frames"] == 64 * n
+    assert "roofline" not in j and "also" not in j
+
+
 @pytest.mark.parametrize("n", [2, 4])
 def test_rccl_failure_falls_back_in_process_and_is_flagged(n):
     """SURVEY 8(e) "Fallback": RCCL does not come up -> the SAME processes go on over gloo (no re-exec, no restart), the
     parameter blocks every rank formed itself are compared, the line carries a number and says [REPLICAS ONLY] + the error"""
-    r = _run(["--gpus", str(n), "--dry-run", "--force-rccl-failure"])
+    r = _run(["--gpus", str(n), "--dry-run", "--force-rccl-failure", "--full"])
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout

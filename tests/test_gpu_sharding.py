@@ -73,7 +73,7 @@ def test_bench_py_launches_two_ranks_itself_and_equals_two_single_runs(torch_cud
     """`python bench.py --gpus 2` (no launcher) spawns its two ranks; on this one-GPU box both use cuda:0 over a gloo group.
     128 frames, and the checksum of the filtered output equals the sum of the two shards run as N = 1 jobs."""
     bench = os.path.join(ROOT, "bench.py")
-    common = ["--steps", "2", "--warmup", "1", "--cpu-seconds", "0", "--no-extra", "--no-verify", "--wakeup-ms", "0"]
+    common = ["--steps", "2", "--warmup", "1", "--cpu-seconds", "0", "--no-extra", "--no-verify", "--wakeup-ms", "0", "--full"]
 
     def run(extra):
         r = subprocess.run([sys.executable, bench] + extra + common, capture_output=True, text=True, timeout=600)
@@ -107,7 +107,7 @@ def test_four_ranks_carry_the_1080p_and_chain_legs(torch_cuda):
     share the box's one GPU over gloo, so the aggregate is about ONE GPU's rate -- the keys, the reductions and the checksum
     are what is checked."""
     j = _bench(["--gpus", "4", "--backend", "gloo", "--share-device", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0", "--no-verify",
-                "--wakeup-ms", "0", "--frames-per-gpu", "16"])
+                "--wakeup-ms", "0", "--frames-per-gpu", "16", "--full"])
     assert j["n_gpus"] == 4 and j["ranks_seen"] == 4 and j["checksum"]["frames"] == 64 and j["rccl"]["wanted"] is False
     fhd, chain = j["roofline"]["fhd_w19"], j["also"]["vga_chain_batch64"]
     assert fhd["n_gpus"] == 4 and len(fhd["k1_ms_per_rank"]) == 4 and fhd["window"] == 19 and fhd["width"] == 1920

@@ -1,6 +1,6 @@
 set -x
 mkdir -p gpurun_out/r04l
-C="--steps 20 --warmup 5 --cpu-seconds 0 --no-verify --no-extra"
+C="--full --steps 20 --warmup 5 --cpu-seconds 0 --no-verify --no-extra"
 show() { python -c "
 import json,sys
 j=json.loads([l for l in open('$1') if l.startswith('{')][-1])

@@ -9,7 +9,7 @@
 #   pmc_feeders PMC passes over tools/bench_feeders.py (Buffer2D::updateData over 128 distinct 1080p frames, projectiveToReal
 #               on 4.2 GB): HBM traffic of the streaming kernels on working sets far beyond the Infinity Cache
 #   stats       rocprofv3 --kernel-trace --stats over the default bench command, the chain and SPDSR
-#   bench       the plain bench line
+#   bench       the bench line with every side measurement (bench.py --full)
 #   chain       tools/bench_chain.py at 1080p and 640x480, tools/bench_spdsr.py, tools/bench_mrf.py
 #   sweep       K1 variant / tile sweeps (BASELINE config 3)
 #   micro       tools/valu_microbench (VALU issue costs) -> valu_costs.json (tools/valu_costs.py)
@@ -45,7 +45,7 @@ pmc_passes() {   # <subdir> <program> <args...>: five passes of the same command
 for STEP in $STEPS; do
 case $STEP in
 pmc_bench)
-  SHORT="bench.py --steps 3 --warmup 1 --wakeup-ms 0 --cpu-seconds 0 --no-verify"
+  SHORT="bench.py --full --steps 3 --warmup 1 --wakeup-ms 0 --cpu-seconds 0 --no-verify"
   pmc_passes pmc_bench python3 $SHORT
   python3 tools/pmc_report.py --dir "$OUT/pmc_bench" --out "$OUT/pmc_bench.json" --command "python3 $SHORT" \
       --algo tools/algo_bytes_bench.json 2> "$OUT/pmc_bench.summary"
@@ -114,13 +114,13 @@ pmc_feeders)
 stats)
   # headline leg only (wake-up + W + K steps of the 64 x VGA window-11 Process, and the 32 x 1080p window-19 side leg are
   # separate kernels): the kernel's average in the stats file is then over steady-clock launches, like the bench line's
-  rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o stats -- python3 bench.py --cpu-seconds 0 --no-verify --no-idle-leg --no-extra > "$OUT/bench_under_rocprof.json" 2> "$OUT/bench_under_rocprof.err"
-  rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_full" -o stats -- python3 bench.py --cpu-seconds 0 --no-verify > "$OUT/bench_full_under_rocprof.json" 2> "$OUT/bench_full_under_rocprof.err"
+  rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o stats -- python3 bench.py --full --cpu-seconds 0 --no-verify --no-idle-leg --no-extra > "$OUT/bench_under_rocprof.json" 2> "$OUT/bench_under_rocprof.err"
+  rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_full" -o stats -- python3 bench.py --full --cpu-seconds 0 --no-verify > "$OUT/bench_full_under_rocprof.json" 2> "$OUT/bench_full_under_rocprof.err"
   rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/chain_stats" -o chain -- python3 tools/bench_chain.py > /dev/null 2> "$OUT/chain_stats.err"
   rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/spdsr_stats" -o spdsr -- python3 tools/bench_spdsr.py > /dev/null 2> "$OUT/spdsr_stats.err"
   ;;
 bench)
-  python3 bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+  python3 bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
   cat "$OUT/bench.json"
   ;;
 chain)
@@ -142,10 +142,10 @@ sweep)
   } > "$OUT/sweep_k1_variants.log" 2> "$OUT/sweep.err"
   ;;
 shard)
-  python3 bench.py --cpu-seconds 0 --no-extra --no-verify --dump-frames /tmp/kde_frames.bin > "$OUT/shard_bench_py.json" 2> "$OUT/shard.err"
-  examples/shard_replay --frames 64 --frames-file /tmp/kde_frames.bin > "$OUT/shard_replay_same_frames.json" 2>> "$OUT/shard.err"
+  python3 bench.py --full --cpu-seconds 0 --no-extra --no-verify --dump-frames "$OUT/frames.bin" > "$OUT/shard_bench_py.json" 2> "$OUT/shard.err"
+  examples/shard_replay --frames 64 --frames-file "$OUT/frames.bin" > "$OUT/shard_replay_same_frames.json" 2>> "$OUT/shard.err"
   examples/shard_replay --frames 64 > "$OUT/shard_replay_builtin_frames.json" 2>> "$OUT/shard.err"
-  rm -f /tmp/kde_frames.bin
+  rm -f "$OUT/frames.bin"
   python3 - "$OUT" <<'PY'
 import json, sys
 out = sys.argv[1]
