@@ -705,16 +705,14 @@ __device__ __forceinline__ uint32_t add_byte3(uint32_t w, uint32_t acc)
     return r;
 }
 
-// FUSED_LABEL = false keeps r03's form of the pass-1 label test (weight times a {0,1} mask: one packed instruction more per
-// unit) for the A/B of tools/bench_chain.py (KDE_K10_MASK_PRODUCT=1); the outputs are bit-identical
-// KDE_K10_WAVES = waves per SIMD the register allocator must leave room for (0 = no bound: 80 VGPRs, 6 workgroups per CU).
+// FUSED_LABEL = false is r03's form of the pass-1 label test (weight times a {0,1} mask: one packed instruction more per
+// unit, bit-identical); only the fused form is launched (EXPERIMENTS.md)
+// kK10Waves = waves per SIMD the register allocator must leave room for (0 = no bound: 80 VGPRs, 6 workgroups per CU).
 // A single 1080p frame is 4050 workgroups: on 6 x 256 slots that is 2.64 rounds (the third 64 % full), on 8 x 256 it is
-// 1.98 -- tools/ab_k10_waves.sh measures whether the 6 spilled registers of the 64-VGPR build cost less than the tail.
-#ifndef KDE_K10_WAVES
-#define KDE_K10_WAVES 0
-#endif
+// 1.98 -- measured with 7 and 8 waves (64 VGPRs, 6 spilled registers): no gain over the unbounded build (EXPERIMENTS.md).
+constexpr int kK10Waves = 0;
 template <bool FUSED_LABEL>
-__global__ __launch_bounds__(kE7BX* kE7BY) __attribute__((amdgpu_waves_per_eu(KDE_K10_WAVES ? KDE_K10_WAVES : 1))) void enhance7_pk_kernel(const Enh7PkDev a)
+__global__ __launch_bounds__(kE7BX* kE7BY) __attribute__((amdgpu_waves_per_eu(kK10Waves ? kK10Waves : 1))) void enhance7_pk_kernel(const Enh7PkDev a)
 {
     constexpr int WIN = 7, R = 3, HALF = 3, SEGP = 4;
     constexpr int NT = kE7BX * kE7BY;
@@ -1233,12 +1231,7 @@ static int launch_ers_enhance_one(int width, int height, int n, const float* rd,
         KDE_STAGE(d.stage_avg = g_stage.ers_avg; d.stage_dev = g_stage.ers_dev; d.stage_counters = g_stage.counters;
                   d.stage_force = g_stage.force_full_rules;)
         const dim3 grid((unsigned)(ceil_div(width, kE7BX * 2) * ceil_div(height, kE7BY) * n));
-#ifdef KDE_AB_SWITCHES
-        static const bool mask_product = KDE_AB_ENV("KDE_K10_MASK_PRODUCT") != nullptr;  // r03's pass-1 label test (tools/ab_k10.py)
-        if (mask_product) hipLaunchKernelGGL(enhance7_pk_kernel<false>, grid, dim3(kE7BX * kE7BY), 0, s, d);
-        else
-#endif
-            hipLaunchKernelGGL(enhance7_pk_kernel<true>, grid, dim3(kE7BX * kE7BY), 0, s, d);
+        hipLaunchKernelGGL(enhance7_pk_kernel<true>, grid, dim3(kE7BX * kE7BY), 0, s, d);
         KDE_HIP_TRY(hipGetLastError());
         return KDE_OK;
     }

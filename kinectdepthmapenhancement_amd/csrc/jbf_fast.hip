@@ -27,7 +27,6 @@
 #include "kde_internal.h"
 #include "kde_device_math.h"
 
-#include <cstddef>
 #include <type_traits>
 
 namespace kde {
@@ -274,14 +273,12 @@ __device__ __forceinline__ f2 pk_mul_clamp(f2 a, f2 b)
 // below share one kernel, and without it the window-19 instance grew from 131 to 182 VGPRs (3 -> 2 waves per SIMD)
 // (windows >= 23: at least 3 waves per SIMD, i.e. <= 168 VGPRs -- without the bound the instances without the colour rule
 //  came out at 228 / 248 registers, 2 waves per SIMD)
-// CR = window rows whose pass-1 arguments are kept for pass 2 (CACHE: all of them, the windows <= 7; 0: recomputed).  0 < CR < WIN
-// is r05's partial form for windows 9..13: the first CR rows are unrolled and their arguments stay in registers (two waves per
-// SIMD asked for: 256 registers per lane), the remaining rows run the recomputing loop.  Measured slower (see kVariants): only
-// the measurement build instantiates it.
+// CR = window rows whose pass-1 arguments are kept for pass 2: all of them with CACHE (the windows <= 7), none otherwise
+// (recomputed).  r05's partial form (0 < CR < WIN at windows 9..13) was measured slower and removed (EXPERIMENTS.md).
 template <int WIN, int NP, int BX, int BY, bool CACHE, bool CSKIP, bool VL, bool ELIDE_ON = true, int CR = (CACHE ? WIN : 0)>
-__global__ __launch_bounds__(BX* BY) __attribute__((amdgpu_waves_per_eu(WIN >= 23 ? 3 : ((CR > 0 && !CACHE) ? 2 : 1)))) void jbf_pk_kernel(const FastArgs a)
+__global__ __launch_bounds__(BX* BY) __attribute__((amdgpu_waves_per_eu(WIN >= 23 ? 3 : 1))) void jbf_pk_kernel(const FastArgs a)
 {
-    static_assert(CR >= 0 && CR <= WIN && (!CACHE || CR == WIN), "cached rows");
+    static_assert(CR == (CACHE ? WIN : 0), "cached rows: all or none");
     constexpr int R = WIN / 2;
     constexpr int PX = 2 * NP;
     constexpr int NT = BX * BY;
@@ -530,12 +527,6 @@ __global__ __launch_bounds__(BX* BY) __attribute__((amdgpu_waves_per_eu(WIN >= 2
             // compiler issue per-lane global_load_dwordx4 and hold the pairs in VGPRs: 248 instead of ~150 registers)
             typedef const f2 __attribute__((address_space(4)))* cf2p;
             lsj = *(cf2p)(uintptr_t)(a.tab_dev + (i * WIN + u) * 2);
-        } else if constexpr (CR > 0 && !CACHE) {
-            // the partial-keep instances: read the pair straight from the kernel-argument segment (the argument block IS
-            // FastArgs).  Through `a.tab` the compiler copied the whole 3.6 KB block to scratch in the instances with the colour rule.
-            typedef const f2 __attribute__((address_space(4)))* cf2p;
-            typedef const char __attribute__((address_space(4)))* ccp;
-            lsj = *(cf2p)((ccp)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(FastArgs, tab) + (size_t)((i * WIN + u) * 2) * sizeof(float));
         } else {
             lsj = *reinterpret_cast<const f2*>(&a.tab[(i * WIN + u) * 2]);
         }
@@ -718,9 +709,6 @@ struct Variant {
     {"w" #WIN "-pk" #NP "-" #BX "x" #BY "-" #CACHE "-v1", WIN, true, &launch_pk_variant<WIN, NP, BX, BY, CACHE, false>}
 #define KN(WIN, NP, BX, BY, CACHE) \
     {"w" #WIN "-pk" #NP "-" #BX "x" #BY "-" #CACHE "-v4-noelide", WIN, true, &launch_pk_variant<WIN, NP, BX, BY, CACHE, true, false>}
-// r05 experiment: the first CR window rows keep their pass-1 arguments (VGPRs + AccVGPRs at two waves per SIMD)
-#define KC(WIN, NP, BX, BY, CR) \
-    {"w" #WIN "-pk" #NP "-" #BX "x" #BY "-keep" #CR "-v4", WIN, true, &launch_pk_variant<WIN, NP, BX, BY, false, true, true, CR>}
 const Variant kVariants[] = {
     // the FIRST variant listed for a window is the built-in choice (interleaved A/B sweep on MI355X,
     // profiles/r03_sweep_k1_variants.log); the others stay selectable for the tile sweep of BASELINE config 3.
@@ -749,23 +737,12 @@ const Variant kVariants[] = {
     K(21, 1, 16, 16, false), K(21, 2, 16, 16, false),
     // windows 23..31: the log2(S) table no longer fits the argument block and comes from a device copy (FastArgs::tab_dev)
     K(23, 1, 16, 16, false), K(25, 1, 16, 16, false), K(27, 1, 16, 16, false), K(29, 1, 16, 16, false), K(31, 1, 16, 16, false),
-#ifdef KDE_AB_SWITCHES
-    // r05: part of the pass-1 arguments kept in registers at two waves per SIMD.  Bit-identical, and
-    // SLOWER at windows 11 and 13 (+5 .. +12 %), a wash at window 9 (-0.6 % on 64 x 640x480, +1.6 .. +5 % at 1080p):
-    // profiles/r05_sweep_k1_variants.log (tools/ab_k1_keep.py).  The allocator keeps everything in the 256 architectural
-    // VGPRs (agpr_count 0: on gfx950 the file is unified, AccVGPRs would only add capacity at ONE wave per SIMD), so what is
-    // bought is 8 of 20 issue slots on the kept units and what is paid is the occupancy (2 instead of 4-6 waves per SIMD:
-    // the v_exp_f32 / LDS latency is no longer covered) and 2-3 x the code per body.  Measurement build only; K1 is closed.
-    KC(9, 1, 16, 16, 9), KC(9, 1, 16, 16, 5), KC(9, 2, 16, 16, 4), KC(11, 1, 16, 16, 5), KC(11, 1, 16, 16, 7), KC(11, 2, 16, 16, 3),
-    KC(13, 1, 16, 16, 4), KC(13, 1, 16, 16, 6),
-#endif
 };
 static_assert(sizeof(FastArgs) <= 4096, "FastArgs is passed by value as the kernel-argument block");
 #undef V
 #undef K
 #undef KS
 #undef KN
-#undef KC
 constexpr int kNumVariants = sizeof(kVariants) / sizeof(kVariants[0]);
 
 }  // namespace

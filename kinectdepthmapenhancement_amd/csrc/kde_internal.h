@@ -33,18 +33,6 @@ int fail(int code, const char* fmt, ...);   // records the message for kde_last_
         if (rc_ != KDE_OK) return rc_; \
     } while (0)
 
-// A/B switches (environment variables that select a rejected or alternative kernel) exist only in the measurement build
-// tools/hooks/libkde_hip_ab.so (-DKDE_AB_SWITCHES): the product library reads no environment variable and carries none of
-// the kernels that were measured slower and dropped.  KDE_AB_ENV(name) is getenv there and a constant nullptr here.
-#ifdef KDE_AB_SWITCHES
-#include <cstdlib>
-#define KDE_AB_ENV(name) (::getenv(name))
-#define KDE_AB(...) __VA_ARGS__
-#else
-#define KDE_AB_ENV(name) (static_cast<const char*>(nullptr))
-#define KDE_AB(...)
-#endif
-
 #define KDE_REQUIRE(cond, ...)                                   \
     do {                                                         \
         if (!(cond)) return ::kde::fail(KDE_ERR_INVALID, __VA_ARGS__); \
@@ -227,17 +215,8 @@ int launch_ers_enhance(int width, int height, int n, const float* rd, const uint
 int launch_spdsr_init_normalized(const Camera& c, float* nxy, hipStream_t s);
 int launch_spdsr_cluster_planes(int width, int height, int n, int nclusters, int table_frames, const int32_t* labels,
                                 const kde_float3* pts, double* sums, double* cov, float* nd, int* moments_dirty, hipStream_t s);
-// state of the resident sweep launches of one SPDSR handle (spdsr_kernels.hip: mrf_sweeps_resident_kernel)
-struct SpdsrResident {
-    int* flags = nullptr;       // device: one announcement counter per workgroup, a 128-byte line each
-    int* status = nullptr;      // pinned host: 0, or (workgroup + 1) that gave up waiting
-    int gen = 0;                // the counters run on across calls
-    int cus = 0, cooperative = 0;
-};
-int spdsr_resident_init(SpdsrResident* r);
-void spdsr_resident_release(SpdsrResident* r);
 int launch_spdsr_plane_projection(int width, int height, int n, int nclusters, const float* nd, const int32_t* labels,
                                   const kde_float3* pts, const float* nxy, kde_float3* plane_fitted, kde_float3* opt_a,
-                                  kde_float3* opt_b, int sweeps, kde_float3** result, SpdsrResident* res, hipStream_t s);
+                                  kde_float3* opt_b, int sweeps, kde_float3** result, hipStream_t s);
 
 }  // namespace kde

@@ -632,134 +632,3 @@ def test_spdsr_object_reuse_starts_from_clean_moment_tables(torch_cuda, F, oracl
     nd, opt = host(many.getClusterND_Device()), host(many.getOptimizedPoints_Device())
     for slot, f in ((0, 2), (1, 3)):
         same((nd[slot], opt[slot]), fresh(f))
-
-
-def test_spdsr_two_sweeps_per_launch_equal_single_sweeps_bitwise(torch_cuda, tmp_path):
-    """The measured-and-rejected two-sweeps-per-launch form of Projection_GPU's 20 mrf_optimization sweeps
-    (mrf_sweep2_kernel; only in the measurement build tools/hooks/libkde_hip_ab.so, selected there by KDE_SPDSR_TWO_SWEEPS=1,
-    read once per process): per pixel the arithmetic is the single-sweep kernel's, so the optimised cloud must not change by
-    a bit against the PRODUCT library's.  Ragged size: partial tiles and an odd width."""
-    import os
-    import subprocess
-    import sys
-    from conftest import ROOT
-    code = (
-        "import os, sys, numpy as np, torch; sys.path.insert(0, %r)\n"
-        "if os.environ.get('KDE_SPDSR_TWO_SWEEPS'):\n"
-        "    sys.path.insert(0, os.path.join(sys.path[0], 'tools', 'hooks')); import ab; ab.use_ab_library()\n"
-        "from kinectdepthmapenhancement_amd import filters as F, synth\n"
-        "from oracle import oracle as O\n"
-        "outs = []\n"
-        "for (w, h, g) in ((203, 131, (5, 7)), (320, 240, (6, 8))):\n"
-        "    bgr, depth = synth.make_frame(33, w, h); K = synth.intrinsics(w, h)\n"
-        "    pts = O.p2r_depth(depth, K).view(np.float32).reshape(h, w, 3)\n"
-        "    sr = F.SPDepthSuperResolution(w, h); sr.SetParametor(g[0], g[1], K)\n"
-        "    sr.Process(torch.from_numpy(depth).cuda(), torch.from_numpy(np.ascontiguousarray(pts)).cuda(), torch.from_numpy(bgr).cuda())\n"
-        "    outs.append(sr.getOptimizedPoints_Device().cpu().numpy().ravel())\n"
-        "np.save(sys.argv[1], np.concatenate(outs))\n") % ROOT
-    res = []
-    for tag, extra in (("two", {"KDE_SPDSR_TWO_SWEEPS": "1"}), ("one", {})):
-        path = str(tmp_path / f"opt_{tag}.npy")
-        r = subprocess.run([sys.executable, "-c", code, path], env=dict(os.environ, **extra), capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stderr[-2000:]
-        res.append(np.load(path))
-    assert res[0].shape == res[1].shape and np.isfinite(res[0]).mean() > 0.9
-    assert np.array_equal(res[0].view(np.uint32), res[1].view(np.uint32))
-
-
-_RESIDENT_CHILD = (
-    "import os, sys, threading, numpy as np, torch; sys.path.insert(0, %r)\n"
-    "sys.path.insert(0, os.path.join(sys.path[0], 'tools', 'hooks')); import ab; ab.use_ab_library()\n"
-    "from kinectdepthmapenhancement_amd import filters as F, synth\n"
-    "from oracle import oracle as O\n"
-    "def run(seed, w, h, g, reps, stream=None):\n"
-    "    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):\n"
-    "        bgr, depth = synth.make_frame(seed, w, h); K = synth.intrinsics(w, h)\n"
-    "        pts = O.p2r_depth(depth, K).view(np.float32).reshape(h, w, 3)\n"
-    "        sr = F.SPDepthSuperResolution(w, h); sr.SetParametor(g[0], g[1], K)\n"
-    "        a = (torch.from_numpy(depth).cuda(), torch.from_numpy(np.ascontiguousarray(pts)).cuda(), torch.from_numpy(bgr).cuda())\n"
-    "        for _ in range(reps): sr.Process(*a)\n"
-    "        return np.asarray(sr.getOptimizedPoints_Host()).copy().ravel()\n"
-    "cases, threads = %r, int(sys.argv[2])\n"
-    "outs = [None] * len(cases)\n"
-    "if threads:\n"
-    "    run(*cases[0], 1)\n"
-    "    th = [threading.Thread(target=lambda i=i: outs.__setitem__(i, run(*cases[i], 25, torch.cuda.Stream()))) for i in range(len(cases))]\n"
-    "    [t.start() for t in th]; [t.join(120) for t in th]\n"
-    "    assert not any(t.is_alive() for t in th)\n"
-    "else:\n"
-    "    outs = [run(*c, 4) for c in cases]\n"
-    "np.save(sys.argv[1], np.concatenate(outs))\n")
-
-
-def _resident_child(tmp_path, cases, mode, threads=0):
-    import os
-    import subprocess
-    import sys
-    from conftest import ROOT
-    path = str(tmp_path / f"opt_resident_{mode}_{threads}.npy")
-    r = subprocess.run([sys.executable, "-c", _RESIDENT_CHILD % (ROOT, cases), path, str(threads)], env=dict(os.environ, KDE_SPDSR_RESIDENT=str(mode)),
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return np.load(path)
-
-
-def test_spdsr_resident_sweeps_equal_the_20_launches_bitwise(torch_cuda, F, oracle, synth, tmp_path):
-    """The measured-and-rejected LDS-resident form of Projection_GPU's 20 mrf_optimization sweeps (mrf_sweeps_resident_kernel:
-    one launch, one block of the frame per CU, only the 2-pixel rims go through memory between sweeps; measurement build only,
-    KDE_SPDSR_RESIDENT = 1 cooperative / 2 plain launch).  Per pixel the arithmetic is mrf_sweep_kernel's, so the optimised
-    cloud must equal the PRODUCT library's 20 launches bit for bit, call after call (the announcement counters run on).
-    Sizes: 1080p (blocks of 120 x 68), 640x480, and a ragged frame with an odd width and partial last blocks."""
-    cases = ((33, 1920, 1080, (15, 20)), (33, 640, 480, (15, 20)), (33, 203, 131, (5, 7)))
-    want = []
-    for seed, w, h, g in cases:
-        bgr, depth = synth.make_frame(seed, w, h)
-        K = synth.intrinsics(w, h)
-        pts = oracle.p2r_depth(depth, K).view(np.float32).reshape(h, w, 3)
-        sr = F.SPDepthSuperResolution(w, h)
-        sr.SetParametor(g[0], g[1], K)
-        sr.Process(dev(torch_cuda, depth), dev(torch_cuda, np.ascontiguousarray(pts)), dev(torch_cuda, bgr))
-        want.append(host(sr.getOptimizedPoints_Device()).ravel())
-    want = np.concatenate(want)
-    assert np.isfinite(want).mean() > 0.9
-    for mode in (1, 2):
-        got = _resident_child(tmp_path, cases, mode)
-        assert got.shape == want.shape and np.array_equal(got.view(np.uint32), want.view(np.uint32)), f"resident mode {mode}"
-
-
-def test_spdsr_resident_cooperative_launches_from_three_host_threads(torch_cuda, F, oracle, synth, tmp_path):
-    """three host threads, each with its own stream and SPDSR handle, call Process 25 times concurrently on the measurement build
-    with the COOPERATIVE resident launch: the runtime runs cooperative launches of a device one after the other, so every
-    workgroup of a launch is resident and no launch waits for another's (a spin that gave up would fail the child); results
-    equal the product library's bit for bit"""
-    cases = ((41, 640, 480, (15, 20)), (42, 640, 480, (15, 20)), (43, 640, 480, (15, 20)))
-    want = _resident_child(tmp_path, cases, 0)
-    got = _resident_child(tmp_path, cases, 1, threads=1)
-    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
-
-
-def test_k8_row_coalesced_form_is_bit_identical(torch_cuda, F, oracle, synth, tmp_path):
-    """The measured-and-rejected row-coalesced form of analyzeClusters (analyze_clusters_rows_kernel; measurement build only,
-    KDE_K8_ROWS=1): coalesced 4-pixel chunks per wavefront row, integer sums by the loading lane, the float sums by the owning
-    thread from an LDS stage in the reference's order.  Labels, cluster records and float centres after 2 - 5 iterations must
-    equal the PRODUCT kernel's bit for bit (1080p, 640x480, a ragged frame, two other grids)."""
-    import os
-    import subprocess
-    import sys
-    import zlib
-    from conftest import ROOT
-    cases = ((1920, 1080, (15, 20), 5), (640, 480, (15, 20), 5), (203, 131, (5, 7), 3), (640, 480, (10, 8), 2), (320, 240, (6, 8), 4))
-    want = {}
-    for (w, h, g, it) in cases:
-        bgr, depth = synth.make_frame(33, w, h)
-        K = synth.intrinsics(w, h)
-        pts = oracle.p2r_depth(depth, K).view(np.float32).reshape(h, w, 3)
-        d = F.DepthAdaptiveSuperpixel(w, h)
-        d.SetParametor(g[0], g[1], K)
-        d.Segmentation(dev(torch_cuda, bgr), dev(torch_cuda, np.ascontiguousarray(pts)), 100.0, 20.0, 200.0, it)
-        want[f"{w}x{h}_{g}_{it}"] = tuple(zlib.crc32(host(t).tobytes()) for t in (d.getLabelDevice(), d.getMeanDataDevice(), d.getCentersDevice()))
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "k8_rows_check.py"), ROOT], env=dict(os.environ, KDE_K8_ROWS="1"),
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    got = eval(r.stdout.strip().splitlines()[-1])        # the tool prints one dict literal of CRC triples
-    assert got == want

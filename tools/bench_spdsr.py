@@ -7,9 +7,6 @@ import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "hooks"))
-import ab as _ab                                    # noqa: E402
-_ab.use_ab_library_if_switched()                    # a KDE_* A/B switch in the environment -> tools/hooks/libkde_hip_ab.so
 
 
 def main():
@@ -53,7 +50,7 @@ def main():
         torch.cuda.synchronize()
     wall = (time.perf_counter() - t0) / a.iters * 1e3
     print(json.dumps({"width": W, "height": H, "rows": a.rows, "cols": a.cols, "spdsr_process_ms": ms, "spdsr_process_wall_ms_synced": wall,
-                      "mpix_s": W * H / ms / 1e3, "resident_mode": os.environ.get("KDE_SPDSR_RESIDENT", "product default"),
+                      "mpix_s": W * H / ms / 1e3,
                       "crc_optimized": zlib.crc32(sr.getOptimizedPoints_Device().cpu().numpy().tobytes())}))
 
 
