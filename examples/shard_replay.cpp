@@ -10,6 +10,7 @@
 //
 // usage: shard_replay [--frames N] [--width W] [--height H] [--window 11] [--steps K] [--warmup W] [--wakeup-ms 150]
 //                     [--devices G] [--share-device G] [--frames-file F] [--verify] [--force-rccl-failure] [--rccl-timeout S]
+//                     [--host-fed [--u16] [--chunk C]]
 //   Timing follows bench.py: an untimed wake-up load (an idle MI355X sits at its lowest clock level), W warm-up steps,
 //   then K timed steps that all device threads start together; every step is K0 (kde_jbf_presmooth_batch) + K1
 //   (kde_jbf_filter_batch) -- exactly what kde_jbf_process_batch launches -- bracketed by HIP events on the device's
@@ -25,6 +26,13 @@
 //             block goes the "replicas only" way.
 //   --rccl-timeout S (default 60): ncclCommInitAll runs in a helper thread; if it has not returned after S seconds the
 //             run goes on without RCCL ("replicas only", flagged) and the process leaves through _Exit at the end.
+//   --host-fed [--u16] [--chunk C]: each device thread keeps its shard in pinned host memory (hipHostMalloc) instead of HBM
+//             and a timed step is ONE kde_jbf_feed_process call (copy-in, K0 + K1, copy-out in chunks of C frames, default 8),
+//             as a camera- or file-fed deployment runs; the line adds per-device H2D / D2H GB/s (bytes over the summed event
+//             spans of the copies) and the host-fed Mpixel/s.  --u16: the depth goes over the link as the sensor's uint16 mm
+//             (widened on the device); the frames are rounded to whole mm for every run of the command, so the resident
+//             runs of --verify see the same values.  --verify always runs its one- and two-block legs resident: the
+//             host-fed checksums must equal the resident ones.
 // Fallback: if the RCCL communicators cannot be created, nothing is restarted -- every device thread forms the
 // parameter block itself ("replicas only"), compares it with rank 0's copy in host memory, and the line says so with RCCL's error.
 // prints one JSON line: per-device times and PCI addresses, aggregate Mpixels/s, checksum,
@@ -79,7 +87,8 @@ namespace {
 struct Options {
     int frames = 64, width = 640, height = 480, window = 11, steps = 20, warmup = 5, devices = 0, share_device = 0;
     float spatial_sigma = 3.0f, color_sigma = 7.65f, depth_sigma = 20.0f, wakeup_ms = 150.0f, rccl_timeout_s = 60.0f;
-    bool verify = false, force_rccl_failure = false;
+    bool verify = false, force_rccl_failure = false, host_fed = false, u16 = false;
+    int chunk = 8;
     std::string frames_file;
 };
 
@@ -175,6 +184,7 @@ struct ShardResult {
     double ms_per_step = 0.0;               // wall time of the K timed steps on this device / K (host clock around the sync)
     double k0_ms = 0.0, k1_ms = 0.0;        // mean launch time of the two kernels over the timed steps (HIP events)
     double k1_ms_median = 0.0, k1_ms_min = 0.0;
+    double h2d_gbs = 0.0, d2h_gbs = 0.0;    // --host-fed: bytes over the summed event spans of the copies, timed steps
     int wakeup_steps = 0;
     std::vector<uint64_t> frame_hash;       // one per frame of the shard
     bool table_matches_rank0 = true;
@@ -224,15 +234,9 @@ ShardResult run_shard(const Options& o, int device, int rank, int first, int cou
         else if (root_block) res.table_matches_rank0 = std::memcmp(mine.data(), root_block->data() + 8, mine.size() * sizeof(float)) == 0;
     }
     if (count > 0) {
-        // ---- this shard's frames, resident in this device's HBM ----
-        float* depth_dev = nullptr;
-        uint8_t* bgr_dev = nullptr;
-        float* out_dev = nullptr;
-        HIP_OK(hipMalloc(&depth_dev, px * count * sizeof(float)));
-        HIP_OK(hipMalloc(&bgr_dev, px * count * 3));
-        HIP_OK(hipMalloc(&out_dev, px * count * sizeof(float)));
-        std::vector<uint8_t> bgr;
-        std::vector<float> depth;
+        // ---- this shard's frames: resident in this device's HBM, or (--host-fed) in pinned host memory ----
+        std::vector<uint8_t> bgr(px * 3 * count);
+        std::vector<float> depth(px * count);
         if (!o.frames_file.empty()) {
             // bench.py --dump-frames: o.frames colour frames, then o.frames depth frames
             FILE* fp = std::fopen(o.frames_file.c_str(), "rb");
@@ -240,8 +244,6 @@ ShardResult run_shard(const Options& o, int device, int rank, int first, int cou
                 std::fprintf(stderr, "cannot open %s\n", o.frames_file.c_str());
                 std::exit(2);
             }
-            bgr.resize(px * 3 * count);
-            depth.resize(px * count);
             bool ok = std::fseek(fp, (long)(px * 3 * first), SEEK_SET) == 0 && std::fread(bgr.data(), 1, bgr.size(), fp) == bgr.size();
             ok = ok && std::fseek(fp, (long)(px * 3 * o.frames + px * 4 * first), SEEK_SET) == 0 &&
                  std::fread(depth.data(), 4, depth.size(), fp) == depth.size();
@@ -250,18 +252,62 @@ ShardResult run_shard(const Options& o, int device, int rank, int first, int cou
                 std::fprintf(stderr, "%s is shorter than %d frames of %dx%d\n", o.frames_file.c_str(), o.frames, o.width, o.height);
                 std::exit(2);
             }
-            HIP_OK(hipMemcpy(depth_dev, depth.data(), px * count * sizeof(float), hipMemcpyHostToDevice));
-            HIP_OK(hipMemcpy(bgr_dev, bgr.data(), px * 3 * count, hipMemcpyHostToDevice));
         } else {
+            std::vector<uint8_t> fb;
+            std::vector<float> fd;
             for (int f = 0; f < count; f++) {
-                make_frame(first + f, o.width, o.height, bgr, depth);
-                HIP_OK(hipMemcpy(depth_dev + px * f, depth.data(), px * sizeof(float), hipMemcpyHostToDevice));
-                HIP_OK(hipMemcpy(bgr_dev + px * 3 * f, bgr.data(), px * 3, hipMemcpyHostToDevice));
+                make_frame(first + f, o.width, o.height, fb, fd);
+                std::memcpy(bgr.data() + px * 3 * f, fb.data(), px * 3);
+                std::memcpy(depth.data() + px * f, fd.data(), px * sizeof(float));
             }
         }
+        std::vector<uint16_t> depth16;
+        if (o.u16) {            // the sensor's format: whole millimetres, 0 = invalid; every run of the command sees these values
+            depth16.resize(depth.size());
+            for (size_t i = 0; i < depth.size(); i++) {
+                const float z = depth[i];
+                depth16[i] = (uint16_t)(z > 0.0f ? std::min(65535.0f, std::nearbyint(z)) : 0.0f);
+                depth[i] = (float)depth16[i];
+            }
+        }
+        float* depth_dev = nullptr;
+        uint8_t* bgr_dev = nullptr;
+        float* out_dev = nullptr;
         uint8_t* smooth_dev = nullptr;
-        HIP_OK(hipMalloc(&smooth_dev, px * count * 3));
+        void* depth_host = nullptr;          // --host-fed: pinned copies of the shard, and the pinned output
+        uint8_t* bgr_host = nullptr;
+        float* out_host = nullptr;
+        kde_jbf_feed* feed = nullptr;
+        kde_feed_stats sum{};
+        const size_t dsz = o.u16 ? sizeof(uint16_t) : sizeof(float);
+        if (o.host_fed) {
+            HIP_OK(hipHostMalloc(&depth_host, px * count * dsz, hipHostMallocDefault));
+            HIP_OK(hipHostMalloc(reinterpret_cast<void**>(&bgr_host), px * count * 3, hipHostMallocDefault));
+            HIP_OK(hipHostMalloc(reinterpret_cast<void**>(&out_host), px * count * sizeof(float), hipHostMallocDefault));
+            std::memcpy(depth_host, o.u16 ? static_cast<const void*>(depth16.data()) : static_cast<const void*>(depth.data()), px * count * dsz);
+            std::memcpy(bgr_host, bgr.data(), px * count * 3);
+            KDE_OK_OR_DIE(kde_jbf_feed_create(&feed, jbf, o.chunk));
+        } else {
+            HIP_OK(hipMalloc(&depth_dev, px * count * sizeof(float)));
+            HIP_OK(hipMalloc(&bgr_dev, px * count * 3));
+            HIP_OK(hipMalloc(&out_dev, px * count * sizeof(float)));
+            HIP_OK(hipMalloc(&smooth_dev, px * count * 3));
+            HIP_OK(hipMemcpy(depth_dev, depth.data(), px * count * sizeof(float), hipMemcpyHostToDevice));
+            HIP_OK(hipMemcpy(bgr_dev, bgr.data(), px * count * 3, hipMemcpyHostToDevice));
+        }
         auto step = [&](hipEvent_t* ev) {
+            if (o.host_fed) {                                      // blocking: copy-in, K0 + K1, copy-out of the whole shard
+                KDE_OK_OR_DIE(kde_jbf_feed_process(feed, count, depth_host, o.u16 ? KDE_DEPTH_U16 : KDE_DEPTH_F32, bgr_host, out_host));
+                if (ev) {
+                    kde_feed_stats st;
+                    KDE_OK_OR_DIE(kde_jbf_feed_last_stats(feed, &st));
+                    sum.h2d_ms += st.h2d_ms;
+                    sum.d2h_ms += st.d2h_ms;
+                    sum.h2d_bytes += st.h2d_bytes;
+                    sum.d2h_bytes += st.d2h_bytes;
+                }
+                return;
+            }
             if (ev) HIP_OK(hipEventRecord(ev[0], stream));
             KDE_OK_OR_DIE(kde_jbf_presmooth_batch(jbf, count, bgr_dev, smooth_dev, stream));             // K0
             if (ev) HIP_OK(hipEventRecord(ev[1], stream));
@@ -285,7 +331,7 @@ ShardResult run_shard(const Options& o, int device, int rank, int first, int cou
         HIP_OK(hipStreamSynchronize(stream));
         res.ms_per_step = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() / o.steps;
         std::vector<float> k1(o.steps);
-        for (int k = 0; k < o.steps; k++) {
+        for (int k = 0; k < o.steps && !o.host_fed; k++) {
             float a = 0.0f, b = 0.0f;
             HIP_OK(hipEventElapsedTime(&a, ev[(size_t)k * 3], ev[(size_t)k * 3 + 1]));
             HIP_OK(hipEventElapsedTime(&b, ev[(size_t)k * 3 + 1], ev[(size_t)k * 3 + 2]));
@@ -297,15 +343,25 @@ ShardResult run_shard(const Options& o, int device, int rank, int first, int cou
         res.k1_ms_median = k1[k1.size() / 2];
         res.k1_ms_min = k1.front();
         for (auto& e : ev) HIP_OK(hipEventDestroy(e));
-        HIP_OK(hipFree(smooth_dev));
-        std::vector<float> out(px);
-        for (int f = 0; f < count; f++) {
-            HIP_OK(hipMemcpy(out.data(), out_dev + px * f, px * sizeof(float), hipMemcpyDeviceToHost));
-            res.frame_hash.push_back(fnv(out.data(), px));
+        if (o.host_fed) {
+            res.h2d_gbs = sum.h2d_ms > 0 ? (double)sum.h2d_bytes / (sum.h2d_ms * 1e-3) / 1e9 : 0.0;
+            res.d2h_gbs = sum.d2h_ms > 0 ? (double)sum.d2h_bytes / (sum.d2h_ms * 1e-3) / 1e9 : 0.0;
+            for (int f = 0; f < count; f++) res.frame_hash.push_back(fnv(out_host + px * f, px));
+            KDE_OK_OR_DIE(kde_jbf_feed_destroy(feed));
+            HIP_OK(hipHostFree(depth_host));
+            HIP_OK(hipHostFree(bgr_host));
+            HIP_OK(hipHostFree(out_host));
+        } else {
+            HIP_OK(hipFree(smooth_dev));
+            std::vector<float> out(px);
+            for (int f = 0; f < count; f++) {
+                HIP_OK(hipMemcpy(out.data(), out_dev + px * f, px * sizeof(float), hipMemcpyDeviceToHost));
+                res.frame_hash.push_back(fnv(out.data(), px));
+            }
+            HIP_OK(hipFree(depth_dev));
+            HIP_OK(hipFree(bgr_dev));
+            HIP_OK(hipFree(out_dev));
         }
-        HIP_OK(hipFree(depth_dev));
-        HIP_OK(hipFree(bgr_dev));
-        HIP_OK(hipFree(out_dev));
     }
     else if (barrier) barrier->wait();        // an empty shard still takes part in the common start
     KDE_OK_OR_DIE(kde_jbf_destroy(jbf));
@@ -369,6 +425,9 @@ int main(int argc, char** argv)
         else if (a == "--rccl-timeout") o.rccl_timeout_s = (float)std::atof(next());
         else if (a == "--verify") o.verify = true;
         else if (a == "--force-rccl-failure") o.force_rccl_failure = true;
+        else if (a == "--host-fed") o.host_fed = true;
+        else if (a == "--u16") o.u16 = true;
+        else if (a == "--chunk") o.chunk = std::atoi(next());
         else {
             std::fprintf(stderr, "unknown argument %s\n", a.c_str());
             return 2;
@@ -438,11 +497,17 @@ int main(int argc, char** argv)
     std::string per_dev = "[";
     for (int d = 0; d < G; d++) {
         slowest = std::max(slowest, results[d].ms_per_step);
-        char buf[384];
+        char buf[512];
         std::snprintf(buf, sizeof(buf), "%s{\"device\": %d, \"pci_bus_id\": \"%s\", \"ms_per_step\": %.4f, \"k0_ms\": %.4f, \"k1_ms\": %.4f, "
-                      "\"k1_ms_median\": %.4f, \"k1_ms_min\": %.4f}", d ? ", " : "", d, results[d].pci_bus_id.c_str(), results[d].ms_per_step,
+                      "\"k1_ms_median\": %.4f, \"k1_ms_min\": %.4f", d ? ", " : "", d, results[d].pci_bus_id.c_str(), results[d].ms_per_step,
                       results[d].k0_ms, results[d].k1_ms, results[d].k1_ms_median, results[d].k1_ms_min);
         per_dev += buf;
+        if (o.host_fed) {      // (k0_ms / k1_ms are not measured in this mode: the kernels run inside the feed, 0 above)
+            std::snprintf(buf, sizeof(buf), ", \"h2d_GBs\": %.2f, \"d2h_GBs\": %.2f, \"hostfed_mpixels_per_s\": %.1f", results[d].h2d_gbs,
+                          results[d].d2h_gbs, (double)per * o.width * o.height / (results[d].ms_per_step * 1e-3) / 1e6);
+            per_dev += buf;
+        }
+        per_dev += "}";
         tables_ok = tables_ok && results[d].table_matches_rank0;
         hashes.insert(hashes.end(), results[d].frame_hash.begin(), results[d].frame_hash.end());
     }
@@ -453,22 +518,30 @@ int main(int argc, char** argv)
     bool verified = true;
     if (o.verify) {
         // the same frames on device 0 alone: as one block, and as two half blocks -> per-frame hashes must coincide
-        ShardResult one = run_shard(o, 0, 0, 0, o.frames, nullptr, p);
+        Options r = o;
+        r.host_fed = false;    // resident legs: a host-fed run must reproduce them
+        ShardResult one = run_shard(r, 0, 0, 0, o.frames, nullptr, p);
         const int half = o.frames / 2;
-        ShardResult a = run_shard(o, 0, 0, 0, half, nullptr, p), b = run_shard(o, 0, 0, half, o.frames - half, nullptr, p);
+        ShardResult a = run_shard(r, 0, 0, 0, half, nullptr, p), b = run_shard(r, 0, 0, half, o.frames - half, nullptr, p);
         std::vector<uint64_t> two(a.frame_hash);
         two.insert(two.end(), b.frame_hash.begin(), b.frame_hash.end());
         verified = one.frame_hash == hashes && two == hashes;
     }
     const double mpix = (double)o.frames * o.width * o.height / (slowest * 1e-3) / 1e6;
+    char mbuf[160];
+    std::snprintf(mbuf, sizeof(mbuf), "host-fed (%s depth, chunk %d, pinned host buffers)", o.u16 ? "uint16" : "float", o.chunk);
+    const std::string mode = o.host_fed ? std::string(mbuf) : std::string(o.u16 ? "resident (uint16-rounded frames)" : "resident");
+    std::snprintf(mbuf, sizeof(mbuf), "%.1f", mpix);
+    const std::string hostfed_mpix = o.host_fed ? std::string(mbuf) : std::string("null");
     std::printf("{\"devices\": %d, \"host_threads\": %d, \"frames\": %d, \"frames_per_device\": %d, \"width\": %d, \"height\": %d, \"window\": %d, "
                 "\"steps\": %d, \"warmup\": %d, \"wakeup_steps_before_warmup\": %d, \"input\": \"%s\", "
                 "\"ms_per_step_slowest_device\": %.4f, \"mpixels_per_s\": %.1f, \"per_device\": %s, \"params_broadcast\": \"%s\", "
-                "\"tables_match_rank0\": %s, \"checksum\": \"%016llx\", \"verified\": %s, \"wall_s\": %.2f}\n",
+                "\"tables_match_rank0\": %s, \"checksum\": \"%016llx\", \"verified\": %s, \"wall_s\": %.2f, \"mode\": \"%s\", "
+                "\"hostfed_mpixels_per_s\": %s}\n",
                 shared ? 1 : G, G, o.frames, per, o.width, o.height, o.window, o.steps, o.warmup, results[0].wakeup_steps,
                 o.frames_file.empty() ? "built-in generator" : "frames file (bench.py --dump-frames)", slowest, mpix, per_dev.c_str(),
                 broadcast_how.c_str(), tables_ok ? "true" : "false",
-                (unsigned long long)all, o.verify ? (verified ? "true" : "false") : "null", wall_s);
+                (unsigned long long)all, o.verify ? (verified ? "true" : "false") : "null", wall_s, mode.c_str(), hostfed_mpix.c_str());
     const int rc = (tables_ok && verified) ? 0 : 1;
     if (rccl_stuck) {           // the helper thread is still inside ncclCommInitAll: no static destructor may wait for it
         std::fflush(stdout);

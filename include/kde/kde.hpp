@@ -10,6 +10,7 @@
 //   EdgeRefinedSuperpixel       (EdgeRefinedSuperpixel/EdgeRefinedSuperpixel.h:14-45)
 //   RegionGrowingBilateralFilter(RegionGrowingBilateralFilter.h:11-27)
 //   SPDepthSuperResolution      (SPDepthSuperResolution.h:17-46)
+//   kde::JointBilateralFilterFeed (extension: JointBilateralFilter on frames in host memory, main.cpp:160-163)
 //
 // What differs from the reference headers, and why:
 //   * cv::gpu::GpuMat parameters are templates over "anything with .data/.rows/.cols/.step" — a real
@@ -589,6 +590,40 @@ private:
 };
 
 }  // namespace ref
+
+// ------------------------------------------------------------------------------------------------
+// extension (no reference counterpart): JointBilateralFilter::Process on frames in host memory, the upload of main.cpp:160-163
+// and the uint16 widening of Buffer2D.cpp:18-32 included (kde_jbf_feed_*).  Borrows the filter: it must outlive this object
+// and must not be used while process() runs; its getters keep returning what its own Process wrote.  process() blocks.
+class JointBilateralFilterFeed {
+public:
+    explicit JointBilateralFilterFeed(ref::JointBilateralFilter& jbf, int chunk_frames = 8) : JointBilateralFilterFeed(jbf.handle(), chunk_frames) {}
+    JointBilateralFilterFeed(kde_jbf* jbf, int chunk_frames) { check(kde_jbf_feed_create(&f_, jbf, chunk_frames)); }
+    ~JointBilateralFilterFeed() { kde_jbf_feed_destroy(f_); }
+    JointBilateralFilterFeed(const JointBilateralFilterFeed&) = delete;
+    JointBilateralFilterFeed& operator=(const JointBilateralFilterFeed&) = delete;
+
+    // n frames back to back: depth in mm (float, or the sensor's uint16 with 0 = invalid), packed BGR, filtered depth out
+    void process(int n, const float* depth_host, const uint8_t* bgr_host, float* filtered_host)
+    {
+        check(kde_jbf_feed_process(f_, n, depth_host, KDE_DEPTH_F32, bgr_host, filtered_host));
+    }
+    void process(int n, const uint16_t* depth_host, const uint8_t* bgr_host, float* filtered_host)
+    {
+        check(kde_jbf_feed_process(f_, n, depth_host, KDE_DEPTH_U16, bgr_host, filtered_host));
+    }
+    kde_feed_stats lastStats() const
+    {
+        kde_feed_stats st{};
+        check(kde_jbf_feed_last_stats(f_, &st));
+        return st;
+    }
+    kde_jbf_feed* handle() const { return f_; }
+
+private:
+    kde_jbf_feed* f_ = nullptr;
+};
+
 }  // namespace kde
 
 #ifndef KDE_NO_GLOBAL_NAMES

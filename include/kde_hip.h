@@ -127,6 +127,45 @@ int kde_jbf_active_variant(kde_jbf* h, int* variant);
 int kde_jbf_variant_count(void);
 const char* kde_jbf_variant_name(int variant);
 
+/* ---- host-fed JBF: frames that start and end in host memory --------------------------------------------------------
+ * The reference uploads each frame from cudaMallocHost buffers (main.cpp:160-163) after widening the sensor's uint16 depth
+ * to float on the host (Buffer2D.cpp:18-32).  A feed takes n frames in host memory, copies them to the device in chunks of
+ * chunk_frames, runs K0 + K1 on each chunk (uint16 depth is widened on the device first) and copies the results back,
+ * with the copy-in of one chunk, the kernels of the next older and the copy-out of the one before that overlapped on
+ * three non-blocking streams of its own over a ring of device slots.
+ *
+ * A feed BORROWS its kde_jbf: it reads only the handle's parameters and read-only device tables and writes its own
+ * buffers, so kde_jbf_filtered_device / _filtered_host / _smooth_device still return what the last kde_jbf_* call
+ * wrote.  The handle must outlive the feed, and must not be used (from any thread) while a feed call on it runs.
+ * Like a handle, a feed belongs to the device that was current at creation and is not thread-safe; feeds on separate
+ * handles may run concurrently from different threads.
+ * Host buffers: frame f at base + f * W*H elements (depth, filtered) or base + f * W*H*3 bytes (bgr).  A buffer whose
+ * first and last byte are pinned (hipHostMalloc, hipHostRegister, torch pin_memory()) is copied by DMA directly; its
+ * whole extent must lie inside ONE pinned allocation.  Any other buffer is pageable and is staged by the calling thread
+ * through a pinned ring the feed allocates on first use (inputs before their copy-in, outputs after their copy-out,
+ * overlapping the device work on other chunks). */
+enum { KDE_DEPTH_F32 = 0, KDE_DEPTH_U16 = 1 };   /* u16: millimetres, 0 = invalid (OpenNI XnDepthPixel); widened exactly */
+typedef struct kde_feed_stats {
+    int frames, chunks, chunk_frames;          /* of the last call                                                     */
+    int inputs_staged, outputs_staged;         /* 1 = that side was pageable and went through the feed's pinned ring   */
+    float wall_ms;                             /* host clock, entry to return                                          */
+    float h2d_ms, compute_ms, d2h_ms;          /* sums of the per-chunk HIP-event spans on the feed's three streams   */
+    size_t h2d_bytes, d2h_bytes;
+} kde_feed_stats;
+typedef struct kde_jbf_feed kde_jbf_feed;
+/* chunk_frames in 1..65535 (the bound of kde_jbf_filter_batch); device buffers are sized on the first call */
+int kde_jbf_feed_create(kde_jbf_feed** out, kde_jbf* jbf, int chunk_frames);
+int kde_jbf_feed_destroy(kde_jbf_feed* f);
+/* JointBilateralFilter::Process over n >= 1 frames in host memory (n is not bounded by max_batch): bit-identical to
+ * kde_jbf_process_batch on the same frames.  depth_format = KDE_DEPTH_F32 (float) or KDE_DEPTH_U16 (uint16_t).
+ * BLOCKING: returns once all n outputs are in filtered_host; the inputs may be reused at once.  It synchronises only the
+ * feed's own streams and events, never the device or another stream.  It takes no stream and cannot be captured into a
+ * graph: the one entry point of this header that is not capture-safe. */
+int kde_jbf_feed_process(kde_jbf_feed* f, int n, const void* depth_host, int depth_format, const uint8_t* bgr_host,
+                         float* filtered_host);
+/* what the last kde_jbf_feed_process did (zeros before the first call) */
+int kde_jbf_feed_last_stats(kde_jbf_feed* f, kde_feed_stats* out);
+
 /* ============================================================================================
  * MarkovRandomField — MarkovRandomField/MarkovRandomField.{cpp,cu} (sibling filter)
  * ========================================================================================== */

@@ -29,6 +29,16 @@ class JbfParams(C.Structure):
                 ("presmooth_sigma_color", C.c_float), ("presmooth_sigma_spatial", C.c_float)]
 
 
+KDE_DEPTH_F32, KDE_DEPTH_U16 = 0, 1
+
+
+class FeedStats(C.Structure):
+    """kde_feed_stats: what the last kde_jbf_feed_process call did."""
+    _fields_ = [("frames", C.c_int), ("chunks", C.c_int), ("chunk_frames", C.c_int), ("inputs_staged", C.c_int),
+                ("outputs_staged", C.c_int), ("wall_ms", C.c_float), ("h2d_ms", C.c_float), ("compute_ms", C.c_float),
+                ("d2h_ms", C.c_float), ("h2d_bytes", C.c_size_t), ("d2h_bytes", C.c_size_t)]
+
+
 def build(force: bool = False) -> str:
     """Compile libkde_hip.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     if force:
@@ -64,6 +74,10 @@ SIGNATURES = {
     "kde_jbf_active_variant": (_i, [_vp, C.POINTER(_i)]),
     "kde_jbf_variant_count": (_i, []),
     "kde_jbf_variant_name": (C.c_char_p, [_i]),
+    "kde_jbf_feed_create": (_i, [_pp, _vp, _i]),
+    "kde_jbf_feed_destroy": (_i, [_vp]),
+    "kde_jbf_feed_process": (_i, [_vp, _i, _vp, _i, _vp, _vp]),
+    "kde_jbf_feed_last_stats": (_i, [_vp, C.POINTER(FeedStats)]),
     "kde_mrf_create": (_i, [_pp, _i, _i, _i, _i, _f, _f]),
     "kde_mrf_destroy": (_i, [_vp]),
     "kde_mrf_process_batch": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),

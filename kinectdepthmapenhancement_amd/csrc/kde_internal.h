@@ -182,6 +182,8 @@ int launch_buf_insert_depth(kde_weighted_d* buf, const float* d, size_t n, hipSt
 int launch_buf_insert_float2(kde_weighted_d* buf, const float* xy, int width, int height, hipStream_t s);
 int launch_buf_get(const kde_weighted_d* buf, float* out, size_t n, int which, hipStream_t s);
 int launch_buf_update(kde_weighted_d* buf, const float* d, size_t n, int n_frames, hipStream_t s);
+// host-fed JBF (kde_jbf_feed_process): n uint16 depth samples -> float, exact
+int launch_widen_u16(const uint16_t* src, float* dst, size_t n, hipStream_t s);
 
 struct DaspGeom {
     int width, height, rows, cols, wx, wy;

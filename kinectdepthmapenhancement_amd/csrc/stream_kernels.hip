@@ -405,6 +405,28 @@ __global__ __launch_bounds__(kThreads) void buf_get_scalar_kernel(const kde_weig
     for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += stride) out[i] = which ? buf[i].w : buf[i].d;
 }
 
+
+// ---- host-fed JBF: uint16 depth (OpenNI XnDepthPixel, mm) widened to float on the device ------------------------------
+// (float)u is exact for every uint16.  Eight samples per thread: one 16-byte load, two 16-byte stores.  Default caching,
+// not the NT path: K1 reads the widened chunk right afterwards (8 VGA frames = 9.8 MB stay on-chip).
+__global__ __launch_bounds__(kThreads) void widen_u16_kernel(const uint4* __restrict__ src, float4* __restrict__ dst, size_t n8,
+                                                             const uint16_t* __restrict__ src_tail, float* __restrict__ dst_tail,
+                                                             unsigned ntail)
+{
+    const size_t g = (size_t)blockIdx.x * kThreads + threadIdx.x;
+    if (g < n8) {
+        const uint4 v = src[g];
+        dst[2 * g] = make_float4((float)(v.x & 0xffffu), (float)(v.x >> 16), (float)(v.y & 0xffffu), (float)(v.y >> 16));
+        dst[2 * g + 1] = make_float4((float)(v.z & 0xffffu), (float)(v.z >> 16), (float)(v.w & 0xffffu), (float)(v.w >> 16));
+    }
+    if (g < ntail) dst_tail[g] = (float)src_tail[g];
+}
+
+__global__ __launch_bounds__(kThreads) void widen_u16_scalar_kernel(const uint16_t* __restrict__ src, float* __restrict__ dst, size_t n)
+{
+    const size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i < n) dst[i] = (float)src[i];
+}
 }  // namespace
 
 // vector forms need 16-byte aligned pointers, and for a batch frames that start on 16-byte boundaries (W*H % 4 == 0)
@@ -518,6 +540,20 @@ int launch_buf_update(kde_weighted_d* buf, const float* d, size_t n, int n_frame
     if (vec) hipLaunchKernelGGL(buf_update4_kernel<false>, dim3(grid_for(n / 4)), dim3(kThreads), 0, s, buf, d, n, n_frames);
     if (done < n)
         hipLaunchKernelGGL(buf_update_scalar_kernel, dim3(grid_for(n - done)), dim3(kThreads), 0, s, buf, d, done, n, n_frames);
+    KDE_HIP_TRY(hipGetLastError());
+    return KDE_OK;
+}
+
+int launch_widen_u16(const uint16_t* src, float* dst, size_t n, hipStream_t s)
+{
+    if (n == 0) return KDE_OK;
+    if (aligned(src, 16) && aligned(dst, 16)) {
+        const size_t n8 = n / 8;
+        hipLaunchKernelGGL(widen_u16_kernel, dim3(grid_for(n8 + 1)), dim3(kThreads), 0, s, reinterpret_cast<const uint4*>(src),
+                           reinterpret_cast<float4*>(dst), n8, src + n8 * 8, dst + n8 * 8, (unsigned)(n - n8 * 8));
+    } else {
+        hipLaunchKernelGGL(widen_u16_scalar_kernel, dim3(grid_for(n)), dim3(kThreads), 0, s, src, dst, n);
+    }
     KDE_HIP_TRY(hipGetLastError());
     return KDE_OK;
 }

@@ -161,6 +161,58 @@ class JointBilateralFilter(_Handle):
         return [lib().kde_jbf_variant_name(i).decode() for i in range(n)]
 
 
+def _host_array(a, dtypes, shape, name: str):
+    """(data pointer, numpy dtype) of a host numpy array or CPU torch tensor (pinned or not): contiguous, of one of `dtypes`
+    (numpy dtypes), of `shape`"""
+    if isinstance(a, torch.Tensor):
+        if a.is_cuda:
+            raise TypeError(f"{name}: expected host memory (numpy array or CPU tensor), got a CUDA tensor")
+        tdt = {torch.float32: np.dtype(np.float32), torch.uint8: np.dtype(np.uint8)}
+        if hasattr(torch, "uint16"):
+            tdt[torch.uint16] = np.dtype(np.uint16)
+        dt, contiguous = tdt.get(a.dtype), a.is_contiguous()
+    elif isinstance(a, np.ndarray):
+        dt, contiguous = a.dtype, a.flags.c_contiguous
+    else:
+        raise TypeError(f"{name}: expected a numpy array or a CPU torch tensor, got {type(a).__name__}")
+    if dt not in [np.dtype(d) for d in dtypes] or tuple(a.shape) != tuple(shape) or not contiguous:
+        want = " or ".join(np.dtype(d).name for d in dtypes)
+        raise ValueError(f"{name}: expected contiguous {want} {tuple(shape)}, got {getattr(a, 'dtype', None)} {tuple(a.shape)}")
+    return (a.data_ptr() if isinstance(a, torch.Tensor) else a.ctypes.data), dt
+
+
+class JointBilateralFilterFeed(_Handle):
+    """Host-fed JointBilateralFilter::Process (kde_jbf_feed_*): frames in host memory in, filtered depth in host memory out,
+    in chunks of `chunk_frames` with the copies overlapped with the kernels.  Borrows `jbf` (kept alive by this object) and
+    leaves its device buffers untouched; `jbf` must not be used while process() runs.  A blocking call on the feed's own
+    streams, not on torch's current stream."""
+    _destroy = "kde_jbf_feed_destroy"
+
+    def __init__(self, jbf: JointBilateralFilter, chunk_frames: int = 8):
+        super().__init__()
+        self.jbf = jbf
+        self.Width, self.Height, self.chunk_frames = jbf.Width, jbf.Height, chunk_frames
+        check(lib().kde_jbf_feed_create(C.byref(self._h), jbf._h, chunk_frames))
+
+    def process(self, depth, color, out=None):
+        """depth [n,H,W] float32 or uint16 (mm, 0 = invalid), color [n,H,W,3] uint8 BGR, out [n,H,W] float32 (allocated
+        as a numpy array when None): numpy arrays or CPU torch tensors, pinned or pageable.  Returns out."""
+        n = depth.shape[0] if len(depth.shape) == 3 else -1
+        dptr, ddt = _host_array(depth, (np.float32, np.uint16), (n, self.Height, self.Width), "depth")
+        cptr, _ = _host_array(color, (np.uint8,), (n, self.Height, self.Width, 3), "color")
+        if out is None:
+            out = np.empty((n, self.Height, self.Width), np.float32)
+        optr, _ = _host_array(out, (np.float32,), (n, self.Height, self.Width), "out")
+        fmt = _native.KDE_DEPTH_U16 if ddt == np.uint16 else _native.KDE_DEPTH_F32
+        check(lib().kde_jbf_feed_process(self._h, n, dptr, fmt, cptr, optr))
+        return out
+
+    def last_stats(self) -> dict:
+        st = _native.FeedStats()
+        check(lib().kde_jbf_feed_last_stats(self._h, C.byref(st)))
+        return {name: getattr(st, name) for name, _ in st._fields_}
+
+
 class MarkovRandomField(_Handle):
     """MarkovRandomField/MarkovRandomField.h (sibling filter, same signature as JBF)."""
     _destroy = "kde_mrf_destroy"
