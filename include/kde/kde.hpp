@@ -589,6 +589,45 @@ private:
     void* stream_ = nullptr;
 };
 
+// ------------------------------------------------------------------------------------------------
+// NormalEstimation/NormalMapGenerator.h: per-pixel normals of points in millimetres (projectiveToReal's output)
+class NormalMapGenerator {
+public:
+    static const int SDC = KDE_NORMALS_SDC, CM = KDE_NORMALS_CM, BILATERAL = KDE_NORMALS_BILATERAL;   // NormalMapGenerator.h:28
+    NormalMapGenerator(int w, int h) : Width(w), Height(h) { check(kde_normals_create(&h_, w, h, 1, nullptr)); }
+    ~NormalMapGenerator() { kde_normals_destroy(h_); }
+    NormalMapGenerator(const NormalMapGenerator&) = delete;
+    NormalMapGenerator& operator=(const NormalMapGenerator&) = delete;
+    void setNormalEstimationMethods(int method) { check(kde_normals_set_method(h_, method)); }   // SDC throws UNSUPPORTED
+    void generateNormalMap(float3* vertices_device)
+    {
+        check(kde_normals_generate_batch(h_, 1, reinterpret_cast<const kde_float3*>(vertices_device), nullptr, stream_));
+    }
+    float3* getNormalMap()
+    {
+        kde_float3* p = nullptr;
+        check(kde_normals_normal_map_device(h_, &p));
+        return reinterpret_cast<float3*>(p);
+    }
+    // cv::Mat getNormalImg() (NormalMapGenerator.cu:423-439): (int)(255*(n+1.0)/2) per component, host-side
+    HostImage8UC3& getNormalImg()
+    {
+        const kde_float3* p = nullptr;
+        check(kde_normals_normal_map_host(h_, stream_, &p));
+        if (NormalImg.rows != Height) NormalImg = HostImage8UC3(Height, Width);
+        viewers::render_normals(reinterpret_cast<const float*>(p), NormalImg);
+        return NormalImg;
+    }
+    void setStream(void* hip_stream) { stream_ = hip_stream; }
+    kde_normals* handle() const { return h_; }
+
+private:
+    int Width, Height;
+    kde_normals* h_ = nullptr;
+    void* stream_ = nullptr;
+    HostImage8UC3 NormalImg;
+};
+
 }  // namespace ref
 
 // ------------------------------------------------------------------------------------------------
@@ -634,6 +673,7 @@ using kde::ref::DimensionConvertor;
 using kde::ref::EdgeRefinedSuperpixel;
 using kde::ref::JointBilateralFilter;
 using kde::ref::MarkovRandomField;
+using kde::ref::NormalMapGenerator;
 using kde::ref::RegionGrowingBilateralFilter;
 using kde::ref::SPDepthSuperResolution;
 #endif

@@ -108,6 +108,17 @@ inline void copy_from(const ImageLike& src, HostImage8UC3& dst)
     }
 }
 
+// NormalMapGenerator::getNormalImg (NormalMapGenerator.cu:423-439): p[c] = (int)(255*(n.c+1.0)/2), x y z into bytes 0 1 2
+inline void render_normals(const float* n, HostImage8UC3& img)
+{
+    for (int y = 0; y < img.rows; ++y)
+        for (int x = 0; x < img.cols; ++x) {
+            const float* q = n + (static_cast<size_t>(y) * img.cols + x) * 3;
+            uint8_t* p = img.at(y, x);
+            for (int c = 0; c < 3; ++c) p[c] = static_cast<uint8_t>(static_cast<int>(255 * (q[c] + 1.0) / 2));
+        }
+}
+
 }  // namespace viewers
 }  // namespace kde
 

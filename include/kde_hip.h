@@ -330,6 +330,43 @@ int kde_spdsr_optimized_points_host(kde_spdsr* h, void* stream, const kde_float3
 int kde_spdsr_plane_fitted_points_device(kde_spdsr* h, kde_float3** out);         /* Projection_GPU::GetPlaneFitted3D_Device (:56-58) */
 int kde_spdsr_cluster_nd_device(kde_spdsr* h, float** out);                       /* ClusterND_Device: float4 {normal, distance} per cluster */
 
+/* ============================================================================================
+ * NormalMapGenerator — NormalEstimation/NormalMapGenerator.{h,cpp,cu} with SmoothingAreaMapGenerator and
+ * IntegralImageGenerator: per-pixel surface normals of packed kde_float3 points in millimetres (as
+ * kde_dimconv_projective_to_real_depth writes them).  A bad point is (-1,-1,-1).  Any W x H, batched, asynchronous on the
+ * caller's stream with no host synchronisation and no allocation, so kde_normals_generate_batch can be captured into a
+ * graph.  Definitions N1 / N2 (neighbours by linear index, windows that leave the frame) are in DESIGN.md.
+ * ========================================================================================== */
+typedef struct kde_normals kde_normals;
+enum { KDE_NORMALS_SDC = 0, KDE_NORMALS_CM = 1, KDE_NORMALS_BILATERAL = 2 };   /* NormalMapGenerator.h:28 */
+typedef struct kde_normals_params {
+    int method;                     /* normal_estimation_method_ = BILATERAL  NormalMapGenerator.cpp:15 */
+    float max_depth_change_factor;  /* max_depth_change_factor_ = 0.05f       SmoothingAreaMapGenerator.cpp:15 */
+    float normal_smoothing_size;    /* normal_smoothing_size_ = 20.0f         SmoothingAreaMapGenerator.cpp:16 */
+} kde_normals_params;
+/* fills the reference's defaults: BILATERAL, 0.05f, 20.0f */
+int kde_normals_default_params(kde_normals_params* p);
+/* NormalMapGenerator(int w, int h) (NormalMapGenerator.cpp:11-17).  p == NULL -> defaults.  max_batch >= 1 sizes the
+ * object-owned maps.  method SDC -> KDE_ERR_UNSUPPORTED; max_depth_change_factor must be finite and
+ * normal_smoothing_size finite in [-1e6, 1e6] */
+int kde_normals_create(kde_normals** out, int width, int height, int max_batch, const kde_normals_params* p);
+/* NormalMapGenerator::~NormalMapGenerator (NormalMapGenerator.cpp:19-23) */
+int kde_normals_destroy(kde_normals* h);
+/* void setNormalEstimationMethods(int method) (NormalMapGenerator.cpp:35-37): CM or BILATERAL; SDC -> KDE_ERR_UNSUPPORTED */
+int kde_normals_set_method(kde_normals* h, int method);
+/* void generateNormalMap(float3* vertices_device) (NormalMapGenerator.cu:513-524) over n <= max_batch frames;
+ * normals_dev == NULL writes the object-owned normal map */
+int kde_normals_generate_batch(kde_normals* h, int n, const kde_float3* points_dev,
+                               kde_float3* normals_dev /* NULL: object-owned */, void* stream);
+/* float3* getNormalMap() (NormalMapGenerator.cpp:47-49): object-owned, n frames of the last call that wrote it */
+int kde_normals_normal_map_device(kde_normals* h, kde_float3** out);
+/* host copy of the object-owned normal map (what getNormalImg copies down, NormalMapGenerator.cu:423-426): pinned,
+ * lazily copied on `stream`, which is synchronised */
+int kde_normals_normal_map_host(kde_normals* h, void* stream, const kde_float3** out);
+/* SmoothingAreaMapGenerator::getFinalSmoothingMap (SmoothingAreaMapGenerator.cpp:51-53): object-owned, the frames of the
+ * last call if it ran CM, else KDE_ERR_INVALID (BILATERAL builds no smoothing map) */
+int kde_normals_smoothing_map_device(kde_normals* h, float** out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,6 +30,12 @@ class JbfParams(C.Structure):
 
 
 KDE_DEPTH_F32, KDE_DEPTH_U16 = 0, 1
+KDE_NORMALS_SDC, KDE_NORMALS_CM, KDE_NORMALS_BILATERAL = 0, 1, 2
+
+
+class NormalsParams(C.Structure):
+    """kde_normals_params (defaults = NormalMapGenerator.cpp:15, SmoothingAreaMapGenerator.cpp:15-16)."""
+    _fields_ = [("method", C.c_int), ("max_depth_change_factor", C.c_float), ("normal_smoothing_size", C.c_float)]
 
 
 class FeedStats(C.Structure):
@@ -144,6 +150,14 @@ SIGNATURES = {
     "kde_spdsr_optimized_points_host": (_i, [_vp, _vp, _pp]),
     "kde_spdsr_plane_fitted_points_device": (_i, [_vp, _pp]),
     "kde_spdsr_cluster_nd_device": (_i, [_vp, _pp]),
+    "kde_normals_default_params": (_i, [C.POINTER(NormalsParams)]),
+    "kde_normals_create": (_i, [_pp, _i, _i, _i, C.POINTER(NormalsParams)]),
+    "kde_normals_destroy": (_i, [_vp]),
+    "kde_normals_set_method": (_i, [_vp, _i]),
+    "kde_normals_generate_batch": (_i, [_vp, _i, _vp, _vp, _vp]),
+    "kde_normals_normal_map_device": (_i, [_vp, _pp]),
+    "kde_normals_normal_map_host": (_i, [_vp, _vp, _pp]),
+    "kde_normals_smoothing_map_device": (_i, [_vp, _pp]),
 }
 
 

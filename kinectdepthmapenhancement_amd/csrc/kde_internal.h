@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdint>
@@ -213,6 +214,24 @@ int launch_ers_edge_refining(int width, int height, int n, int window, const int
 int launch_ers_enhance(int width, int height, int n, const float* rd, const uint8_t* bgr, const int32_t* labels,
                        const float* s_eff, const float* table_host, int window, float color_sigma, float depth_sigma,
                        float exp_zero, float* out, int variant, hipStream_t s);
+
+// NormalMapGenerator (normal_kernels.hip): one fixed launch sequence per batch of n frames of millimetre points
+struct NormalsLaunch {
+    int width, height, n, method;   // KDE_NORMALS_CM or KDE_NORMALS_BILATERAL
+    float factor, smoothing;        // max_depth_change_factor, normal_smoothing_size
+    const kde_float3* pts;          // [n][H][W] millimetres
+    kde_float3* out;                // [n][H][W] normals
+    float* fs;                      // [n][H][W] final smoothing map (CM)
+    uint8_t* dci;                   // [n][H][W] depth-change map (CM)
+    int* cmax;                      // [n] ordered-int key of the largest DDSA (CM)
+    float* dt_scratch;              // normals_dt_bands(H) * n * 2 * W floats (CM)
+    uint32_t* cnt;                  // [chunk_frames][H][W] integral of z != 0 (CM)
+    double* sums;                   // [9][chunk_frames][H][W] integrals of x, y, z and the products (CM)
+    int chunk_frames;
+};
+int normals_dt_bands(int height);
+int normals_chunk_frames(int width, int height, int max_batch);
+int launch_normals(const NormalsLaunch& a, hipStream_t s);
 
 int launch_spdsr_init_normalized(const Camera& c, float* nxy, hipStream_t s);
 int launch_spdsr_cluster_planes(int width, int height, int n, int nclusters, int table_frames, const int32_t* labels,

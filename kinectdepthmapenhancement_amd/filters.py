@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _native
-from ._native import JbfParams, check, lib
+from ._native import JbfParams, NormalsParams, check, lib
 
 
 def _stream() -> int:
@@ -243,6 +243,68 @@ class MarkovRandomField(_Handle):
         p = C.c_void_p()
         check(lib().kde_mrf_filtered_host(self._h, _stream(), C.byref(p)))
         return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_float)), shape=(self.Height, self.Width)).copy()
+
+
+class NormalMapGenerator(_Handle):
+    """NormalEstimation/NormalMapGenerator.h: per-pixel normals of float32 points [H, W, 3] in millimetres (what
+    DimensionConvertor.projectiveToReal writes); normals are float32 [H, W, 3], a bad point is (-1, -1, -1)."""
+    _destroy = "kde_normals_destroy"
+    SDC, CM, BILATERAL = _native.KDE_NORMALS_SDC, _native.KDE_NORMALS_CM, _native.KDE_NORMALS_BILATERAL
+
+    def __init__(self, width: int, height: int, max_batch: int = 1, params: Optional[NormalsParams] = None):
+        super().__init__()
+        self.Width, self.Height, self.max_batch = width, height, max_batch
+        check(lib().kde_normals_create(C.byref(self._h), width, height, max_batch, None if params is None else C.byref(params)))
+        self._n = self._n_fs = 1   # frames of the last call in the object-owned normal map / smoothing map
+
+    @staticmethod
+    def default_params() -> NormalsParams:
+        p = NormalsParams()
+        check(lib().kde_normals_default_params(C.byref(p)))
+        return p
+
+    def setNormalEstimationMethods(self, method: int) -> None:
+        check(lib().kde_normals_set_method(self._h, int(method)))
+
+    def generateNormalMap(self, points: torch.Tensor) -> None:
+        """void generateNormalMap(float3* vertices_device) (NormalMapGenerator.cu:513-524)"""
+        _req(points, torch.float32, (self.Height, self.Width, 3), "points")
+        check(lib().kde_normals_generate_batch(self._h, 1, points.data_ptr(), None, _stream()))
+        self._n = self._n_fs = 1
+
+    def generateNormalMapBatch(self, n: int, points: torch.Tensor, out: Optional[torch.Tensor] = None):
+        """n frames [n, H, W, 3]; out=None writes the object-owned map (getNormalMap returns all n frames)"""
+        _req(points, torch.float32, (n, self.Height, self.Width, 3), "points")
+        if out is not None:
+            _req(out, torch.float32, (n, self.Height, self.Width, 3), "out")
+        check(lib().kde_normals_generate_batch(self._h, n, points.data_ptr(), _ptr(out), _stream()))
+        self._n_fs = n
+        if out is None:
+            self._n = n
+        return out
+
+    def _shape(self, n, trailing=()):
+        lead = (n,) if n > 1 else ()
+        return lead + (self.Height, self.Width) + tuple(trailing)
+
+    def getNormalMap(self) -> torch.Tensor:
+        """float3* getNormalMap() (NormalMapGenerator.cpp:47-49): object-owned [H, W, 3] ([n, H, W, 3] after a batch)"""
+        p = C.c_void_p()
+        check(lib().kde_normals_normal_map_device(self._h, C.byref(p)))
+        return _view(p.value, self._shape(self._n, (3,)), torch.float32, self)
+
+    def getNormalMap_Host(self) -> np.ndarray:
+        p = C.c_void_p()
+        check(lib().kde_normals_normal_map_host(self._h, _stream(), C.byref(p)))
+        shape = self._shape(self._n, (3,))
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_float)), shape=shape).copy()
+
+    def getSmoothingMap(self) -> torch.Tensor:
+        """the final smoothing map of the last call, if it ran CM (SmoothingAreaMapGenerator::getFinalSmoothingMap):
+        [H, W] ([n, H, W] after a batch, whichever buffer took the normals)"""
+        p = C.c_void_p()
+        check(lib().kde_normals_smoothing_map_device(self._h, C.byref(p)))
+        return _view(p.value, self._shape(self._n_fs), torch.float32, self)
 
 
 class DimensionConvertor(_Handle):
