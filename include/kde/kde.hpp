@@ -628,6 +628,149 @@ private:
     HostImage8UC3 NormalImg;
 };
 
+// ------------------------------------------------------------------------------------------------
+// SuperpixelSegmentation/NormalAdaptiveSuperpixel.h:15-38 (derived from DepthAdaptiveSuperpixel there; here a class of
+// its own over kde_nasp_* with the inherited members it is used through): superpixels on colour, position, depth and
+// surface normal, the consumer of NormalMapGenerator::getNormalMap() in KinectDepthEnhancement.cpp:65-67
+class NormalAdaptiveSuperpixel {
+public:
+    typedef kde_superpixel superpixel;             // SuperpixelSegmentation.h:17-24
+    typedef kde_label_distance label_distance;     // :26-29
+    NormalAdaptiveSuperpixel(int width, int height) : Width(width), Height(height) { check(kde_nasp_create(&h_, width, height, 1)); }
+    virtual ~NormalAdaptiveSuperpixel() { kde_nasp_destroy(h_); }
+    NormalAdaptiveSuperpixel(const NormalAdaptiveSuperpixel&) = delete;
+    NormalAdaptiveSuperpixel& operator=(const NormalAdaptiveSuperpixel&) = delete;
+
+    template <class MatLike>
+    void SetParametor(int rows, int cols, const MatLike& intrinsic)   // [sic], inherited (DepthAdaptiveSuperpixel.cpp:15-39)
+    {
+        double K[9];
+        intrinsic_to_array(intrinsic, K);
+        check(kde_nasp_set_parameters(h_, rows, cols, K));
+    }
+    template <class GpuMatLike>
+    void Segmentation(const GpuMatLike& color_image, float3* points3d_device, float3* normals_device, float color_sigma,
+                      float spatial_sigma, float depth_sigma, float normal_sigma, int iteration)
+    {
+        require_continuous_8uc3(color_image, Width, Height, "NormalAdaptiveSuperpixel::Segmentation");
+        check(kde_nasp_segmentation(h_, color_image.data, reinterpret_cast<const kde_float3*>(points3d_device),
+                                    reinterpret_cast<const kde_float3*>(normals_device), color_sigma, spatial_sigma, depth_sigma,
+                                    normal_sigma, iteration, stream_));
+    }
+    int* getLabelDevice()
+    {
+        int32_t* p = nullptr;
+        check(kde_nasp_labels_device(h_, &p));
+        return p;
+    }
+    superpixel* getMeanDataDevice()
+    {
+        superpixel* p = nullptr;
+        check(kde_nasp_mean_device(h_, &p));
+        return p;
+    }
+    float3* getCentersDevice()
+    {
+        kde_float3* p = nullptr;
+        check(kde_nasp_centers_device(h_, &p));
+        return reinterpret_cast<float3*>(p);
+    }
+    float3* getNormalsDevice()
+    {
+        kde_float3* p = nullptr;
+        check(kde_nasp_normals_device(h_, &p));
+        return reinterpret_cast<float3*>(p);
+    }
+    float* getNormalsVarianceDevice()
+    {
+        float* p = nullptr;
+        check(kde_nasp_normals_variance_device(h_, &p));
+        return p;
+    }
+    // the *_Host members: object-owned pinned copies, refreshed by a blocking copy on the object's stream
+    float3* getCentersHost()
+    {
+        const kde_float3* p = nullptr;
+        int count = 0;
+        check(kde_nasp_centers_host(h_, stream_, &p, &count));
+        return reinterpret_cast<float3*>(const_cast<kde_float3*>(p));
+    }
+    float3* getNormalsHost()
+    {
+        const kde_float3* p = nullptr;
+        int count = 0;
+        check(kde_nasp_normals_host(h_, stream_, &p, &count));
+        return reinterpret_cast<float3*>(const_cast<kde_float3*>(p));
+    }
+    float* getNormalsVarianceHost()
+    {
+        const float* p = nullptr;
+        int count = 0;
+        check(kde_nasp_normals_variance_host(h_, stream_, &p, &count));
+        return const_cast<float*>(p);
+    }
+    // cv::Mat_<cv::Vec3b> getNormalImg() (NormalAdaptiveSuperpixel.cpp:38-54): per pixel its superpixel's normal as
+    // (unsigned char)(255*(n+1)/2); label -1 (and any label outside the table) renders black instead of indexing element -1
+    HostImage8UC3& getNormalImg()
+    {
+        const int32_t* labels = nullptr;
+        const kde_float3* n = nullptr;
+        int count = 0;
+        check(kde_nasp_labels_host(h_, stream_, &labels));
+        check(kde_nasp_normals_host(h_, stream_, &n, &count));
+        if (normalImage.rows != Height) normalImage = HostImage8UC3(Height, Width);
+        for (int y = 0; y < Height; y++)
+            for (int x = 0; x < Width; x++) {
+                const int32_t id = labels[static_cast<size_t>(y) * Width + x];
+                if (id >= 0 && id < count)
+                    normalImage.set(y, x, viewers::normal_byte(n[id].x), viewers::normal_byte(n[id].y), viewers::normal_byte(n[id].z));
+                else normalImage.set(y, x, 0, 0, 0);
+            }
+        return normalImage;
+    }
+    // ---- viewer members of the base class, as DepthAdaptiveSuperpixel has them ----
+    static const int Line = 0, Average = 1;
+    template <class ImageLike>
+    HostImage8UC3& getSegmentedImage(const ImageLike& input_host, int options)
+    {
+        const int32_t* labels = nullptr;
+        check(kde_nasp_labels_host(h_, stream_, &labels));
+        if (SegmentedColor.rows != Height) SegmentedColor = HostImage8UC3(Height, Width);
+        if (options == Line) {
+            viewers::copy_from(input_host, SegmentedColor);
+            viewers::mark_label_borders(labels, SegmentedColor);
+        } else {
+            const superpixel* mean = nullptr;
+            int count = 0;
+            check(kde_nasp_mean_host(h_, stream_, &mean, &count));
+            for (int y = 0; y < Height; y++)
+                for (int x = 0; x < Width; x++) {
+                    const int32_t id = labels[static_cast<size_t>(y) * Width + x];
+                    if (id >= 0 && id < count) SegmentedColor.set(y, x, mean[id].r, mean[id].g, mean[id].b);
+                    else SegmentedColor.set(y, x, 0, 0, 0);
+                }
+        }
+        return SegmentedColor;
+    }
+    HostImage8UC3& getRandomColorImage()
+    {
+        const int32_t* labels = nullptr;
+        check(kde_nasp_labels_host(h_, stream_, &labels));
+        if (SegmentedRandomColor.rows != Height) SegmentedRandomColor = HostImage8UC3(Height, Width);
+        viewers::render_random_colours(labels, SegmentedRandomColor);
+        return SegmentedRandomColor;
+    }
+    void releaseVideo() {}
+    void setStream(void* hip_stream) { stream_ = hip_stream; }
+    kde_nasp* handle() const { return h_; }
+
+private:
+    int Width, Height;
+    kde_nasp* h_ = nullptr;
+    void* stream_ = nullptr;
+    HostImage8UC3 SegmentedColor, SegmentedRandomColor, normalImage;
+};
+
 }  // namespace ref
 
 // ------------------------------------------------------------------------------------------------
@@ -673,6 +816,7 @@ using kde::ref::DimensionConvertor;
 using kde::ref::EdgeRefinedSuperpixel;
 using kde::ref::JointBilateralFilter;
 using kde::ref::MarkovRandomField;
+using kde::ref::NormalAdaptiveSuperpixel;
 using kde::ref::NormalMapGenerator;
 using kde::ref::RegionGrowingBilateralFilter;
 using kde::ref::SPDepthSuperResolution;

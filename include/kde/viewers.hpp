@@ -2,6 +2,7 @@
 // still compiles and gets the same pictures:
 //   JointBilateralFilter::visualize / MarkovRandomField::visualize   (JointBilateralFilter.cpp:50-79, MarkovRandomField.cpp:50-79)
 //   EdgeRefinedSuperpixel::getSegmentedImage(int) / (image) / getRandomColorImage  (EdgeRefinedSuperpixel.cpp:70-147)
+//   NormalAdaptiveSuperpixel::getNormalImg                           (NormalAdaptiveSuperpixel.cpp:38-54)
 //   SuperpixelSegmentation::getSegmentedImage(image, options) / getRandomColorImage / releaseVideo
 //                                                                    (SuperpixelSegmentation.cpp:50-200)
 // Visualisation is outside the hot path: nothing here touches the GPU, opens a window (the reference's
@@ -117,6 +118,16 @@ inline void render_normals(const float* n, HostImage8UC3& img)
             uint8_t* p = img.at(y, x);
             for (int c = 0; c < 3; ++c) p[c] = static_cast<uint8_t>(static_cast<int>(255 * (q[c] + 1.0) / 2));
         }
+}
+
+// NormalAdaptiveSuperpixel::getNormalImg (NormalAdaptiveSuperpixel.cpp:44-46): (unsigned char)(255.0f*(n+1.0f)/2.0f); a NaN
+// component (the conversion is undefined for it) renders 0
+inline uint8_t normal_byte(float n)
+{
+    const float v = 255.0f * (n + 1.0f) / 2.0f;
+    if (!(v == v)) return 0;
+    const float c = v < -2147483648.0f ? -2147483648.0f : (v > 2147483520.0f ? 2147483520.0f : v);
+    return static_cast<uint8_t>(static_cast<int32_t>(c));
 }
 
 }  // namespace viewers

@@ -367,6 +367,50 @@ int kde_normals_normal_map_host(kde_normals* h, void* stream, const kde_float3**
  * last call if it ran CM, else KDE_ERR_INVALID (BILATERAL builds no smoothing map) */
 int kde_normals_smoothing_map_device(kde_normals* h, float** out);
 
+/* ============================================================================================
+ * NormalAdaptiveSuperpixel — SuperpixelSegmentation/NormalAdaptiveSuperpixel.{h,cpp,cu} (+ the DepthAdaptiveSuperpixel
+ * base): superpixels on colour, position, depth and surface normal; the consumer of NormalMapGenerator's output in
+ * KinectDepthEnhancement.cpp:65-67.  Points are packed kde_float3 in millimetres, a bad normal is (-1,-1,-1).  Batched,
+ * asynchronous on the caller's stream, no allocation after kde_nasp_set_parameters.  Definition and the deviations
+ * NA1-NA5 are in DESIGN.md ("Normal-adaptive superpixels"); every output is bit-identical to tools/nasp_ref.c.
+ * ========================================================================================== */
+typedef struct kde_nasp kde_nasp;
+/* NormalAdaptiveSuperpixel(width,height) (NormalAdaptiveSuperpixel.cpp:4-8); max_batch >= 1 sizes the object's buffers */
+int kde_nasp_create(kde_nasp** out, int width, int height, int max_batch);
+int kde_nasp_destroy(kde_nasp* h);                                                 /* ~NormalAdaptiveSuperpixel (.cpp:9-17) */
+/* void SetParametor(int rows, int cols, cv::Mat_<double> intrinsic) (inherited, DepthAdaptiveSuperpixel.cpp:15-39; initMemory
+ * NormalAdaptiveSuperpixel.cpp:19-37).  Zero-fills mean, centres, normals, variance and LD (NA5).  KDE_ERR_INVALID for
+ * geometries the reference would index out of bounds: width/cols >= 8, height/rows >= 8 (the 8 x 8 candidates),
+ * width/(width/cols) == cols, height >= 6. */
+int kde_nasp_set_parameters(kde_nasp* h, int rows, int cols, const double* K9);
+/* void Segmentation(GpuMat color, float3* points3d, float3* normals, float color_sigma, float spatial_sigma,
+ *                   float depth_sigma, float normal_sigma, int iteration) (NormalAdaptiveSuperpixel.cu:1070-1103).
+ * The weights of the weighted-average pass are host-built tables keyed by (color_sigma, spatial_sigma): a call whose two
+ * sigmas differ from the previous call's rebuilds and uploads them on `stream`; such a call is refused with
+ * KDE_ERR_UNSUPPORTED while `stream` is capturing (call once with the same sigmas first), as is a spatial_sigma whose
+ * table would not fit (weight still non-zero after 2^20 entries on a window larger than that). */
+int kde_nasp_segmentation(kde_nasp* h, const uint8_t* bgr_dev, const kde_float3* points_dev, const kde_float3* normals_dev,
+                          float color_sigma, float spatial_sigma, float depth_sigma, float normal_sigma, int iteration,
+                          void* stream);
+/* the same over n <= max_batch frames back to back; frame f's result is bit-identical to its single-frame call */
+int kde_nasp_segmentation_batch(kde_nasp* h, int n, const uint8_t* bgr_dev, const kde_float3* points_dev,
+                                const kde_float3* normals_dev, float color_sigma, float spatial_sigma, float depth_sigma,
+                                float normal_sigma, int iteration, void* stream);
+/* object-owned device buffers, the frames of the last call back to back */
+int kde_nasp_labels_device(kde_nasp* h, int32_t** out);                 /* getLabelDevice (SuperpixelSegmentation.cpp)       */
+int kde_nasp_mean_device(kde_nasp* h, kde_superpixel** out);            /* getMeanDataDevice                                 */
+int kde_nasp_centers_device(kde_nasp* h, kde_float3** out);             /* getCentersDevice (NormalAdaptiveSuperpixel.h:23)  */
+int kde_nasp_normals_device(kde_nasp* h, kde_float3** out);             /* getNormalsDevice (:25)                            */
+int kde_nasp_normals_variance_device(kde_nasp* h, float** out);         /* getNormalsVarianceDevice (:27)                    */
+int kde_nasp_ld_device(kde_nasp* h, kde_label_distance** out);          /* LD_Device                                         */
+/* pinned host copies, refreshed lazily by a blocking copy on `stream` (the reference copies after every Segmentation,
+ * .cu:1097-1101): the only calls that synchronise.  count = records returned (rows*cols per frame of the last call) */
+int kde_nasp_labels_host(kde_nasp* h, void* stream, const int32_t** out);                              /* Labels_Host */
+int kde_nasp_mean_host(kde_nasp* h, void* stream, const kde_superpixel** out, int* count);             /* meanData_Host */
+int kde_nasp_centers_host(kde_nasp* h, void* stream, const kde_float3** out, int* count);              /* getCentersHost (:22) */
+int kde_nasp_normals_host(kde_nasp* h, void* stream, const kde_float3** out, int* count);              /* getNormalsHost (:24) */
+int kde_nasp_normals_variance_host(kde_nasp* h, void* stream, const float** out, int* count);          /* getNormalsVarianceHost (:26) */
+
 #ifdef __cplusplus
 }
 #endif

@@ -158,6 +158,22 @@ SIGNATURES = {
     "kde_normals_normal_map_device": (_i, [_vp, _pp]),
     "kde_normals_normal_map_host": (_i, [_vp, _vp, _pp]),
     "kde_normals_smoothing_map_device": (_i, [_vp, _pp]),
+    "kde_nasp_create": (_i, [_pp, _i, _i, _i]),
+    "kde_nasp_destroy": (_i, [_vp]),
+    "kde_nasp_set_parameters": (_i, [_vp, _i, _i, _vp]),
+    "kde_nasp_segmentation": (_i, [_vp, _vp, _vp, _vp, _f, _f, _f, _f, _i, _vp]),
+    "kde_nasp_segmentation_batch": (_i, [_vp, _i, _vp, _vp, _vp, _f, _f, _f, _f, _i, _vp]),
+    "kde_nasp_labels_device": (_i, [_vp, _pp]),
+    "kde_nasp_mean_device": (_i, [_vp, _pp]),
+    "kde_nasp_centers_device": (_i, [_vp, _pp]),
+    "kde_nasp_normals_device": (_i, [_vp, _pp]),
+    "kde_nasp_normals_variance_device": (_i, [_vp, _pp]),
+    "kde_nasp_ld_device": (_i, [_vp, _pp]),
+    "kde_nasp_labels_host": (_i, [_vp, _vp, _pp]),
+    "kde_nasp_mean_host": (_i, [_vp, _vp, _pp, C.POINTER(_i)]),
+    "kde_nasp_centers_host": (_i, [_vp, _vp, _pp, C.POINTER(_i)]),
+    "kde_nasp_normals_host": (_i, [_vp, _vp, _pp, C.POINTER(_i)]),
+    "kde_nasp_normals_variance_host": (_i, [_vp, _vp, _pp, C.POINTER(_i)]),
 }
 
 

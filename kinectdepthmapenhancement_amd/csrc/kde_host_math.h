@@ -57,4 +57,41 @@ inline int smallest_cd_reaching(float den, float thr)
     return lo;
 }
 
+// ---- NormalAdaptiveSuperpixel ------------------------------------------------------------
+// NA3: acos(normal_diff) < 3.141592653f / 3.0f (NormalAdaptiveSuperpixel.cu:805) is decided on the argument,
+// normal_diff > t: t is the largest float whose double acos, rounded to float, is not below the float constant
+inline float nasp_acos_threshold()
+{
+    const float c = 3.141592653f / 3.0f;
+    float t = 0.5f;
+    for (int i = 0; i < 64 && (float)std::acos((double)t) >= c; i++) t = std::nextafterf(t, 1.0f);
+    for (int i = 0; i < 128 && !((float)std::acos((double)t) >= c); i++) t = std::nextafterf(t, 0.0f);
+    return t;
+}
+
+// NA4: expf(-num / (2 * powf(sigma, 2.0f))) (.cu:769, :772) is DEFINED as (float)exp((double)arg), arg the float quotient
+inline float nasp_weight(float num, float sigma)
+{
+    const float arg = -num / (2.0f * (sigma * sigma));
+    return (float)std::exp((double)arg);
+}
+
+// The weights of the integer numerators 0 .. cap-1, truncated at the first that is exactly 0 (the weight does not grow
+// with the numerator, so every later one is 0 too).  Returns the number of entries written (every numerator from there on weighs 0 if
+// *reached_zero, else the table covers all of 0 .. cap-1).
+inline int nasp_weight_table(float sigma, long long cap, float* table, bool* reached_zero)
+{
+    *reached_zero = false;
+    long long i = 0;
+    for (; i < cap; i++) {
+        const float w = nasp_weight((float)i, sigma);
+        if (w == 0.0f) {
+            *reached_zero = true;
+            break;
+        }
+        table[i] = w;
+    }
+    return (int)i;
+}
+
 }  // namespace kde

@@ -206,6 +206,32 @@ int launch_dasp_analyze_dual(const DaspGeom& g, int n, const uint8_t* bgr, const
                              kde_superpixel* mean_a, kde_float3* centers_a, const int32_t* labels_b, kde_superpixel* mean_b,
                              kde_float3* centers_b, const float* intr_dev, hipStream_t s);
 
+// NormalAdaptiveSuperpixel (nasp_kernels.hip): n frames back to back, per-frame colour / cloud / normals / tables / outputs
+struct NaspLaunch {
+    DaspGeom g;
+    int n;
+    const uint8_t* bgr;            // [n][H][W][3]
+    const kde_float3* pts;         // [n][H][W] millimetres
+    const kde_float3* nrm;         // [n][H][W]
+    kde_label_distance* ld;        // [n][H][W]
+    int32_t* labels;               // [n][H][W]
+    kde_superpixel* mean;          // [n][rows*cols]
+    kde_float3* centers;           // [n][rows*cols]
+    kde_float3* spn;               // [n][rows*cols] superpixel normals
+    float* variance;               // [n][rows*cols]
+    const float* intr;             // 9 floats
+    const float* ctab;             // NA4: colour weight by integer colour distance, ctab_n entries (0 beyond)
+    const float* stab;             // NA4: spatial weight by integer squared pixel distance, stab_n entries (0 beyond)
+    int ctab_n, stab_n;
+    float kc, ks, kd, kn;          // (sigma / sum of sigmas)^2 as .cu:256-258 forms them
+    float win2;                    // ((wx + wy) / 2)^2
+    float acos_thr;                // NA3
+    int reset_on;                  // depth_sigma != 0 || normal_sigma != 0 (.cu:349)
+};
+int launch_nasp_sample(const NaspLaunch& a, hipStream_t s);
+int launch_nasp_calc_ld(const NaspLaunch& a, bool first, hipStream_t s);
+int launch_nasp_clusters(const NaspLaunch& a, hipStream_t s);   // analyzeClusters_NASP + calculateWeightedAverage
+
 int launch_ers_edge_phase(int width, int height, int dir, int window, const int32_t* color_labels, const int32_t* l0,
                           const float* d0, int32_t* l1, float* d1, hipStream_t s);
 int launch_ers_edge_refining(int width, int height, int n, int window, const int32_t* color_labels, const int32_t* l0,

@@ -442,6 +442,112 @@ class DepthAdaptiveSuperpixel(_Handle):
         return self._get("kde_dasp_ld_device", (self.height, self.width, 8), torch.uint8)
 
 
+class NormalAdaptiveSuperpixel(_Handle):
+    """SuperpixelSegmentation/NormalAdaptiveSuperpixel.h:15-38: superpixels on colour, position, depth and surface normal.
+    After segmentation_batch the getters return the n frames of the call ([n, ...]); after Segmentation one frame."""
+    _destroy = "kde_nasp_destroy"
+
+    def __init__(self, width: int, height: int, max_batch: int = 1):
+        super().__init__()
+        self.width, self.height, self.max_batch = width, height, max_batch
+        self.rows = self.cols = 0
+        self._n = 1
+        check(lib().kde_nasp_create(C.byref(self._h), width, height, max_batch))
+
+    def SetParametor(self, rows: int, cols: int, intrinsic) -> None:
+        k = _K9(intrinsic)
+        check(lib().kde_nasp_set_parameters(self._h, rows, cols, k.ctypes.data))
+        self.rows, self.cols = rows, cols
+
+    def Segmentation(self, color_image: torch.Tensor, points3d_device: torch.Tensor, normals_device: torch.Tensor,
+                     color_sigma: float, spatial_sigma: float, depth_sigma: float, normal_sigma: float, iteration: int) -> None:
+        hw = (self.height, self.width)
+        _req(color_image, torch.uint8, hw + (3,), "color_image")
+        _req(points3d_device, torch.float32, hw + (3,), "points3d_device")
+        _req(normals_device, torch.float32, hw + (3,), "normals_device")
+        check(lib().kde_nasp_segmentation(self._h, color_image.data_ptr(), points3d_device.data_ptr(), normals_device.data_ptr(),
+                                          color_sigma, spatial_sigma, depth_sigma, normal_sigma, iteration, _stream()))
+        self._n = 1
+
+    def segmentation_batch(self, color: torch.Tensor, points: torch.Tensor, normals: torch.Tensor, color_sigma: float,
+                           spatial_sigma: float, depth_sigma: float, normal_sigma: float, iteration: int) -> None:
+        """n independent frames back to back ([n,H,W,3] each); each frame's result is bit-identical to its Segmentation"""
+        n = color.shape[0]
+        hw = (self.height, self.width)
+        _req(color, torch.uint8, (n,) + hw + (3,), "color")
+        _req(points, torch.float32, (n,) + hw + (3,), "points")
+        _req(normals, torch.float32, (n,) + hw + (3,), "normals")
+        check(lib().kde_nasp_segmentation_batch(self._h, n, color.data_ptr(), points.data_ptr(), normals.data_ptr(), color_sigma,
+                                                spatial_sigma, depth_sigma, normal_sigma, iteration, _stream()))
+        self._n = n
+
+    def _lead(self):
+        return () if self._n == 1 else (self._n,)
+
+    def _get(self, fn, shape, dtype):
+        p = C.c_void_p()
+        check(getattr(lib(), fn)(self._h, C.byref(p)))
+        return _view(p.value, self._lead() + tuple(shape), dtype, self)
+
+    def getLabelDevice(self) -> torch.Tensor:
+        return self._get("kde_nasp_labels_device", (self.height, self.width), torch.int32)
+
+    def getMeanDataDevice(self) -> torch.Tensor:
+        """superpixel records as raw bytes [rows*cols, 16] (r,g,b,pad, x:int32, y:int32, size:int32)."""
+        return self._get("kde_nasp_mean_device", (self.rows * self.cols, 16), torch.uint8)
+
+    def getCentersDevice(self) -> torch.Tensor:
+        return self._get("kde_nasp_centers_device", (self.rows * self.cols, 3), torch.float32)
+
+    def getNormalsDevice(self) -> torch.Tensor:
+        return self._get("kde_nasp_normals_device", (self.rows * self.cols, 3), torch.float32)
+
+    def getNormalsVarianceDevice(self) -> torch.Tensor:
+        return self._get("kde_nasp_normals_variance_device", (self.rows * self.cols,), torch.float32)
+
+    def getLDDevice(self) -> torch.Tensor:
+        """label_distance records as raw bytes [H,W,8] (d:float32, l:int32)."""
+        return self._get("kde_nasp_ld_device", (self.height, self.width, 8), torch.uint8)
+
+    def _host(self, fn, ctype, per, dtype):
+        p, cnt = C.c_void_p(), C.c_int()
+        check(getattr(lib(), fn)(self._h, _stream(), C.byref(p), C.byref(cnt)))
+        a = np.ctypeslib.as_array(C.cast(p, C.POINTER(ctype)), shape=(cnt.value * per,)).copy()
+        return a.view(dtype).reshape(self._lead() + (self.rows * self.cols, -1))
+
+    def getLabelsHost(self) -> np.ndarray:
+        p = C.c_void_p()
+        check(lib().kde_nasp_labels_host(self._h, _stream(), C.byref(p)))
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_int32)), shape=self._lead() + (self.height, self.width)).copy()
+
+    def getMeanDataHost(self) -> np.ndarray:
+        """records as raw bytes [rows*cols, 16]"""
+        return self._host("kde_nasp_mean_host", C.c_uint8, 16, np.uint8)
+
+    def getCentersHost(self) -> np.ndarray:
+        return self._host("kde_nasp_centers_host", C.c_float, 3, np.float32)
+
+    def getNormalsHost(self) -> np.ndarray:
+        return self._host("kde_nasp_normals_host", C.c_float, 3, np.float32)
+
+    def getNormalsVarianceHost(self) -> np.ndarray:
+        return self._host("kde_nasp_normals_variance_host", C.c_float, 1, np.float32)[..., 0]
+
+    def getNormalImg(self) -> np.ndarray:
+        """NormalAdaptiveSuperpixel.cpp:38-54: per pixel its superpixel's normal as (unsigned char)(255*(n+1)/2); a pixel
+        without a superpixel (label -1) or with a label outside the table is black"""
+        labels, nrm = self.getLabelsHost(), self.getNormalsHost()
+        k = self.rows * self.cols
+        labels, nrm = labels.reshape(-1, self.height, self.width), nrm.reshape(-1, k, 3)
+        img = np.zeros(labels.shape + (3,), np.uint8)
+        for f in range(labels.shape[0]):
+            ok = (labels[f] >= 0) & (labels[f] < k)
+            v = np.float32(255.0) * (nrm[f][np.where(ok, labels[f], 0)] + np.float32(1.0)) / np.float32(2.0)
+            v = np.where(np.isfinite(v), v, 0.0)
+            img[f] = np.where(ok[..., None], np.clip(np.trunc(v), -2147483648, 2147483647).astype(np.int64) & 0xFF, 0).astype(np.uint8)
+        return img.reshape(self._lead() + (self.height, self.width, 3))
+
+
 class EdgeRefinedSuperpixel(_Handle):
     """EdgeRefinedSuperpixel/EdgeRefinedSuperpixel.h:14-45."""
     _destroy = "kde_ers_destroy"
