@@ -10,6 +10,7 @@
 //   EdgeRefinedSuperpixel       (EdgeRefinedSuperpixel/EdgeRefinedSuperpixel.h:14-45)
 //   RegionGrowingBilateralFilter(RegionGrowingBilateralFilter.h:11-27)
 //   SPDepthSuperResolution      (SPDepthSuperResolution.h:17-46)
+//   LabelEquivalenceSeg         (LabelEquivalenceSeg/LabelEquivalenceSeg.h:7-49)
 //   kde::JointBilateralFilterFeed (extension: JointBilateralFilter on frames in host memory, main.cpp:160-163)
 //
 // What differs from the reference headers, and why:
@@ -45,6 +46,7 @@
 #ifndef KDE_HAVE_VECTOR_TYPES
 struct float2 { float x, y; };
 struct float3 { float x, y, z; };
+struct float4 { float x, y, z, w; };
 #endif
 
 namespace kde {
@@ -771,6 +773,88 @@ private:
     HostImage8UC3 SegmentedColor, SegmentedRandomColor, normalImage;
 };
 
+// ------------------------------------------------------------------------------------------------
+// LabelEquivalenceSeg/LabelEquivalenceSeg.h:7-49: merges 4-adjacent superpixels with similar plane parameters into regions
+// (kde_les_*), the consumer of NormalAdaptiveSuperpixel's cluster outputs in KinectDepthEnhancement.cpp:76.  The reference
+// class sizes every table W*H and never learns how many superpixels there are; here setClusterCount() says it (rows * cols
+// of the segmentation that feeds it) before the first labelImage.
+class LabelEquivalenceSeg {
+public:
+    LabelEquivalenceSeg(int width, int height) : Width(width), Height(height) { check(kde_les_create(&h_, width, height, 1, nullptr)); }
+    ~LabelEquivalenceSeg() { kde_les_destroy(h_); }
+    LabelEquivalenceSeg(const LabelEquivalenceSeg&) = delete;
+    LabelEquivalenceSeg& operator=(const LabelEquivalenceSeg&) = delete;
+
+    void setClusterCount(int n_clusters) { Clusters = n_clusters; }   // added: the length of the three cluster tables
+    // LabelEquivalenceSeg.cu:228-282; variance_device is dead in the reference and never read
+    void labelImage(float3* cluster_normals_device, int* cluster_label_device, float3* cluster_centers_device, float* variance_device)
+    {
+        check(kde_les_label_image(h_, reinterpret_cast<const kde_float3*>(cluster_normals_device), cluster_label_device,
+                                  reinterpret_cast<const kde_float3*>(cluster_centers_device), variance_device, Clusters, stream_));
+    }
+    float4* getMergedClusterND_Device() const
+    {
+        kde_float4* p = nullptr;
+        check(kde_les_merged_nd_device(h_, &p));
+        return reinterpret_cast<float4*>(p);
+    }
+    int* getMergedClusterLabel_Device() const
+    {
+        int32_t* p = nullptr;
+        check(kde_les_merged_label_device(h_, &p));
+        return p;
+    }
+    float* getMergedClusterVariance_Device() const
+    {
+        float* p = nullptr;
+        check(kde_les_merged_variance_device(h_, &p));
+        return p;
+    }
+    int* getMergedClusterSize_Device() const
+    {
+        int32_t* p = nullptr;
+        check(kde_les_merged_size_device(h_, &p));
+        return p;
+    }
+    // the *_Host members: object-owned pinned copies, refreshed by a blocking copy on the object's stream
+    float4* getMergedClusterND_Host() const
+    {
+        const kde_float4* p = nullptr;
+        check(kde_les_merged_nd_host(h_, stream_, &p));
+        return reinterpret_cast<float4*>(const_cast<kde_float4*>(p));
+    }
+    int* getMergedClusterLabel_Host() const
+    {
+        const int32_t* p = nullptr;
+        check(kde_les_merged_label_host(h_, stream_, &p));
+        return const_cast<int32_t*>(p);
+    }
+    // cv::Mat_<cv::Vec3b> getSegmentResult() (LabelEquivalenceSeg.cpp:87-108): one colour per merged label, black where it is -1
+    HostImage8UC3& getSegmentResult()
+    {
+        if (show.rows != Height) show = HostImage8UC3(Height, Width);
+        viewers::render_merged_labels(getMergedClusterLabel_Host(), show);
+        return show;
+    }
+    // cv::Mat_<cv::Vec3b> getNormalImg() (LabelEquivalenceSeg.cpp:109-124)
+    HostImage8UC3& getNormalImg()
+    {
+        if (normalImage.rows != Height) normalImage = HostImage8UC3(Height, Width);
+        viewers::render_merged_normals(getMergedClusterLabel_Host(), reinterpret_cast<const float*>(getMergedClusterND_Host()), normalImage);
+        return normalImage;
+    }
+    void viewSegmentResult() { (void)getSegmentResult(); }   // .cpp:63-86 without the .avi writer and cv::imshow
+    void releaseVideo() {}
+    void setStream(void* hip_stream) { stream_ = hip_stream; }
+    kde_les* handle() const { return h_; }
+
+private:
+    int Width, Height, Clusters = 0;
+    kde_les* h_ = nullptr;
+    void* stream_ = nullptr;
+    HostImage8UC3 show, normalImage;
+};
+
 }  // namespace ref
 
 // ------------------------------------------------------------------------------------------------
@@ -815,6 +899,7 @@ using kde::ref::DepthAdaptiveSuperpixel;
 using kde::ref::DimensionConvertor;
 using kde::ref::EdgeRefinedSuperpixel;
 using kde::ref::JointBilateralFilter;
+using kde::ref::LabelEquivalenceSeg;
 using kde::ref::MarkovRandomField;
 using kde::ref::NormalAdaptiveSuperpixel;
 using kde::ref::NormalMapGenerator;

@@ -3,6 +3,7 @@
 //   JointBilateralFilter::visualize / MarkovRandomField::visualize   (JointBilateralFilter.cpp:50-79, MarkovRandomField.cpp:50-79)
 //   EdgeRefinedSuperpixel::getSegmentedImage(int) / (image) / getRandomColorImage  (EdgeRefinedSuperpixel.cpp:70-147)
 //   NormalAdaptiveSuperpixel::getNormalImg                           (NormalAdaptiveSuperpixel.cpp:38-54)
+//   LabelEquivalenceSeg::getSegmentResult / getNormalImg             (LabelEquivalenceSeg.cpp:87-124)
 //   SuperpixelSegmentation::getSegmentedImage(image, options) / getRandomColorImage / releaseVideo
 //                                                                    (SuperpixelSegmentation.cpp:50-200)
 // Visualisation is outside the hot path: nothing here touches the GPU, opens a window (the reference's
@@ -128,6 +129,38 @@ inline uint8_t normal_byte(float n)
     if (!(v == v)) return 0;
     const float c = v < -2147483648.0f ? -2147483648.0f : (v > 2147483520.0f ? 2147483520.0f : v);
     return static_cast<uint8_t>(static_cast<int32_t>(c));
+}
+
+// LabelEquivalenceSeg::getSegmentResult (LabelEquivalenceSeg.cpp:87-108): color_pool[label] where the merged label is > -1,
+// black elsewhere.  The pool is a fixed function of the label (the reference fills it with rand() in its constructor, so
+// only "one stable colour per label" is kept): a 32-bit hash of 12345 + label
+inline void render_merged_labels(const int32_t* labels, HostImage8UC3& img)
+{
+    for (int y = 0; y < img.rows; y++)
+        for (int x = 0; x < img.cols; x++) {
+            const int32_t id = labels[static_cast<size_t>(y) * img.cols + x];
+            if (!(id > -1)) {
+                img.set(y, x, 0, 0, 0);
+                continue;
+            }
+            uint32_t h = (12345u + static_cast<uint32_t>(id)) * 1664525u + 1013904223u;
+            h ^= h >> 16;
+            h *= 2246822519u;
+            h ^= h >> 13;
+            img.set(y, x, static_cast<uint8_t>(h), static_cast<uint8_t>(h >> 8), static_cast<uint8_t>(h >> 16));
+        }
+}
+
+// LabelEquivalenceSeg::getNormalImg (LabelEquivalenceSeg.cpp:109-124): the region's normal as (unsigned char)(255.0f*(n+1.0f)/2.0f)
+// per channel, black where the merged label is -1; nd is float4 per pixel
+inline void render_merged_normals(const int32_t* labels, const float* nd, HostImage8UC3& img)
+{
+    for (int y = 0; y < img.rows; y++)
+        for (int x = 0; x < img.cols; x++) {
+            const size_t i = static_cast<size_t>(y) * img.cols + x;
+            if (labels[i] == -1) img.set(y, x, 0, 0, 0);
+            else img.set(y, x, normal_byte(nd[4 * i]), normal_byte(nd[4 * i + 1]), normal_byte(nd[4 * i + 2]));
+        }
 }
 
 }  // namespace viewers

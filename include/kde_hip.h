@@ -411,6 +411,50 @@ int kde_nasp_centers_host(kde_nasp* h, void* stream, const kde_float3** out, int
 int kde_nasp_normals_host(kde_nasp* h, void* stream, const kde_float3** out, int* count);              /* getNormalsHost (:24) */
 int kde_nasp_normals_variance_host(kde_nasp* h, void* stream, const float** out, int* count);          /* getNormalsVarianceHost (:26) */
 
+/* ============================================================================================
+ * LabelEquivalenceSeg — LabelEquivalenceSeg/LabelEquivalenceSeg.{h,cpp,cu}: merges 4-adjacent superpixels whose plane
+ * parameters are similar (angle between normals below max_angle, plane distances within max_plane_distance) by label
+ * equivalence, then gives every merged region an averaged plane (n, d), a size and a normal-agreement "variance"; the
+ * consumer of NormalAdaptiveSuperpixel's four cluster outputs in KinectDepthEnhancement.cpp:76.  Batched, asynchronous on
+ * the caller's stream, capturable, no allocation and no host synchronisation after kde_les_create.  Definition and the
+ * deviations L1-L7 are in DESIGN.md ("Superpixel merging"); every output is bit-identical to tools/les_ref.c.
+ * n_clusters is the length of the per-superpixel tables (the reference class sizes everything W*H and cannot know it):
+ * 1 <= n_clusters <= min(W*H, 2048); a larger count is refused with KDE_ERR_INVALID (the graph step keeps its tables in
+ * LDS and the adjacency takes n_clusters^2 bits per frame).  A label outside [0, n_clusters) is a pixel without superpixel.
+ * ========================================================================================== */
+typedef struct kde_les kde_les;
+typedef struct kde_float4 { float x, y, z, w; } kde_float4;         /* CUDA float4, 16 B                  */
+typedef struct kde_les_params {
+    int   iterations;               /* 10 rounds of scan + analysis      LabelEquivalenceSeg.cu:235 (>= 0)            */
+    float max_angle;                /* 3.141592653f / 8.0f radians       :40                                          */
+    float max_plane_distance;       /* 150.0f millimetres                :42                                          */
+} kde_les_params;
+/* fills the reference's constants: 10, 3.141592653f / 8.0f, 150.0f */
+int kde_les_default_params(kde_les_params* p);
+/* LabelEquivalenceSeg(int width, int height) (LabelEquivalenceSeg.cpp:7-38).  p == NULL -> defaults; max_batch >= 1
+ * sizes the object-owned buffers.  iterations >= 0; max_angle and max_plane_distance must not be NaN */
+int kde_les_create(kde_les** out, int width, int height, int max_batch, const kde_les_params* p);
+int kde_les_destroy(kde_les* h);                                    /* ~LabelEquivalenceSeg (.cpp:41-59) */
+/* void labelImage(float3* cluster_normals_device, int* cluster_label_device, float3* cluster_centers_device,
+ *                 float* variance_device) (LabelEquivalenceSeg.cu:228-282).  variance_dev is dead in the reference (its only
+ * use is commented out, :82): kept for the signature, may be NULL, never read */
+int kde_les_label_image(kde_les* h, const kde_float3* normals_dev, const int32_t* labels_dev, const kde_float3* centers_dev,
+                        const float* variance_dev, int n_clusters, void* stream);
+/* the same over n <= max_batch frames back to back: labels [n][H][W], per-superpixel inputs [n][n_clusters] (as
+ * NormalAdaptiveSuperpixel lays its outputs out); frame f's result is bit-identical to its single-frame call */
+int kde_les_label_image_batch(kde_les* h, int n, const kde_float3* normals_dev, const int32_t* labels_dev,
+                              const kde_float3* centers_dev, const float* variance_dev, int n_clusters, void* stream);
+/* object-owned device buffers, the frames of the last call back to back */
+int kde_les_merged_label_device(kde_les* h, int32_t** out);         /* getMergedClusterLabel_Device (.cpp:128): [n][H][W], -1 = none */
+int kde_les_merged_nd_device(kde_les* h, kde_float4** out);         /* getMergedClusterND_Device (.cpp:125): [n][H][W], 0 where label -1 */
+/* indexed by merged label, n_clusters entries per frame of the last call, 0 for labels that are nobody's merged label */
+int kde_les_merged_variance_device(kde_les* h, float** out);        /* getMergedClusterVariance_Device (.cpp:137) */
+int kde_les_merged_size_device(kde_les* h, int32_t** out);          /* getMergedClusterSize_Device (.cpp:143)     */
+/* pinned host copies, refreshed lazily by a blocking copy on `stream` (the reference copies the labels after every
+ * labelImage, .cu:278): the only calls that synchronise */
+int kde_les_merged_label_host(kde_les* h, void* stream, const int32_t** out);       /* getMergedClusterLabel_Host (.cpp:134) */
+int kde_les_merged_nd_host(kde_les* h, void* stream, const kde_float4** out);       /* getMergedClusterND_Host (.cpp:131)    */
+
 #ifdef __cplusplus
 }
 #endif

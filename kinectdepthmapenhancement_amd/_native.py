@@ -38,6 +38,11 @@ class NormalsParams(C.Structure):
     _fields_ = [("method", C.c_int), ("max_depth_change_factor", C.c_float), ("normal_smoothing_size", C.c_float)]
 
 
+class LesParams(C.Structure):
+    """kde_les_params (defaults = LabelEquivalenceSeg.cu:235, :40, :42)."""
+    _fields_ = [("iterations", C.c_int), ("max_angle", C.c_float), ("max_plane_distance", C.c_float)]
+
+
 class FeedStats(C.Structure):
     """kde_feed_stats: what the last kde_jbf_feed_process call did."""
     _fields_ = [("frames", C.c_int), ("chunks", C.c_int), ("chunk_frames", C.c_int), ("inputs_staged", C.c_int),
@@ -174,6 +179,17 @@ SIGNATURES = {
     "kde_nasp_centers_host": (_i, [_vp, _vp, _pp, C.POINTER(_i)]),
     "kde_nasp_normals_host": (_i, [_vp, _vp, _pp, C.POINTER(_i)]),
     "kde_nasp_normals_variance_host": (_i, [_vp, _vp, _pp, C.POINTER(_i)]),
+    "kde_les_default_params": (_i, [C.POINTER(LesParams)]),
+    "kde_les_create": (_i, [_pp, _i, _i, _i, C.POINTER(LesParams)]),
+    "kde_les_destroy": (_i, [_vp]),
+    "kde_les_label_image": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "kde_les_label_image_batch": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp]),
+    "kde_les_merged_label_device": (_i, [_vp, _pp]),
+    "kde_les_merged_nd_device": (_i, [_vp, _pp]),
+    "kde_les_merged_variance_device": (_i, [_vp, _pp]),
+    "kde_les_merged_size_device": (_i, [_vp, _pp]),
+    "kde_les_merged_label_host": (_i, [_vp, _vp, _pp]),
+    "kde_les_merged_nd_host": (_i, [_vp, _vp, _pp]),
 }
 
 

@@ -57,17 +57,36 @@ inline int smallest_cd_reaching(float den, float thr)
     return lo;
 }
 
+// ---- acos decided on its argument -----------------------------------------------------------
+// acos(d) < c becomes d > t: t is the largest float in [-1, 1] whose double acos, rounded to float, is not below the float
+// constant c.  c <= 0 or NaN: +inf (nothing passes); c above pi: the float just below -1 (every d in [-1, 1] passes, a d
+// below -1 has a NaN acos and fails).  (float)acos((double)t) does not grow with t, so the boundary is found by bisection
+// on the floats in value order.
+inline float acos_threshold(float c)
+{
+    auto key = [](float f) { uint32_t u; memcpy(&u, &f, 4); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); };
+    auto unkey = [](uint32_t k) { const uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k; float f; memcpy(&f, &u, 4); return f; };
+    auto reaches = [c](float t) { return (float)std::acos((double)t) >= c; };
+    if (c != c) return INFINITY;
+    if (!reaches(-1.0f)) return std::nextafterf(-1.0f, -INFINITY);
+    if (reaches(1.0f)) return INFINITY;
+    uint32_t lo = key(-1.0f), hi = key(1.0f);   // reaches at lo, not at hi
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (reaches(unkey(mid))) lo = mid;
+        else hi = mid;
+    }
+    return unkey(lo);
+}
+
 // ---- NormalAdaptiveSuperpixel ------------------------------------------------------------
 // NA3: acos(normal_diff) < 3.141592653f / 3.0f (NormalAdaptiveSuperpixel.cu:805) is decided on the argument,
-// normal_diff > t: t is the largest float whose double acos, rounded to float, is not below the float constant
-inline float nasp_acos_threshold()
-{
-    const float c = 3.141592653f / 3.0f;
-    float t = 0.5f;
-    for (int i = 0; i < 64 && (float)std::acos((double)t) >= c; i++) t = std::nextafterf(t, 1.0f);
-    for (int i = 0; i < 128 && !((float)std::acos((double)t) >= c); i++) t = std::nextafterf(t, 0.0f);
-    return t;
-}
+// normal_diff > t
+inline float nasp_acos_threshold() { return acos_threshold(3.141592653f / 3.0f); }
+
+// ---- LabelEquivalenceSeg ------------------------------------------------------------------------
+// compNormal's acos(d) > 0 && acos(d) < max_angle (LabelEquivalenceSeg.cu:39-40) is d < 1.0f && d > t
+inline float les_acos_threshold(float max_angle) { return acos_threshold(max_angle); }
 
 // NA4: expf(-num / (2 * powf(sigma, 2.0f))) (.cu:769, :772) is DEFINED as (float)exp((double)arg), arg the float quotient
 inline float nasp_weight(float num, float sigma)

@@ -232,6 +232,28 @@ int launch_nasp_sample(const NaspLaunch& a, hipStream_t s);
 int launch_nasp_calc_ld(const NaspLaunch& a, bool first, hipStream_t s);
 int launch_nasp_clusters(const NaspLaunch& a, hipStream_t s);   // analyzeClusters_NASP + calculateWeightedAverage
 
+// LabelEquivalenceSeg::labelImage (les_kernels.hip): n frames back to back; per-superpixel inputs and tables are strided by nc
+constexpr int kLesMaxClusters = 2048;   // the graph step keeps its per-superpixel tables in LDS (56 KB at 2048)
+struct LesLaunch {
+    int width, height, n;
+    int nc, wpr;                   // superpixels per frame (L1), adjacency words per row = ceil(nc / 32)
+    const kde_float3* normals;     // [n][nc]
+    const int32_t* labels;         // [n][H][W]
+    const kde_float3* centers;     // [n][nc]
+    int32_t* count;                // [n][nc] pixels per superpixel; all zero between calls, like adj
+    uint32_t* adj;                 // [n][nc][wpr] bit B of row A: some pixel of A has an L2-neighbour in B
+    int32_t* list;                 // [n][nc * wpr] indices of the adjacency words that kept a bit
+    int32_t* mfin;                 // [n][nc] merged label per superpixel after the rounds and countKernel's test
+    float4* mnd;                   // [n][nc] merged (n, d) by merged label
+    int32_t* merged_label;         // [n][H][W]
+    float4* merged_nd;             // [n][H][W]
+    float* variance;               // [n][nc] by merged label
+    int32_t* size;                 // [n][nc] by merged label
+    int iterations;
+    float thr, max_dist;           // L6 threshold of max_angle; max_plane_distance
+};
+int launch_les_label_image(const LesLaunch& a, hipStream_t s);   // 3 kernels
+
 int launch_ers_edge_phase(int width, int height, int dir, int window, const int32_t* color_labels, const int32_t* l0,
                           const float* d0, int32_t* l1, float* d1, hipStream_t s);
 int launch_ers_edge_refining(int width, int height, int n, int window, const int32_t* color_labels, const int32_t* l0,

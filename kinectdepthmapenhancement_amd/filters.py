@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _native
-from ._native import JbfParams, NormalsParams, check, lib
+from ._native import JbfParams, LesParams, NormalsParams, check, lib
 
 
 def _stream() -> int:
@@ -546,6 +546,101 @@ class NormalAdaptiveSuperpixel(_Handle):
             v = np.where(np.isfinite(v), v, 0.0)
             img[f] = np.where(ok[..., None], np.clip(np.trunc(v), -2147483648, 2147483647).astype(np.int64) & 0xFF, 0).astype(np.uint8)
         return img.reshape(self._lead() + (self.height, self.width, 3))
+
+
+class LabelEquivalenceSeg(_Handle):
+    """LabelEquivalenceSeg/LabelEquivalenceSeg.h: merges 4-adjacent superpixels with similar plane parameters into regions
+    and gives each region an averaged plane (n, d), a size and a normal-agreement variance.  The number of superpixels is
+    the length of the normals tensor ([k, 3] for labelImage, [n, k, 3] for label_image_batch).  After label_image_batch the
+    getters return the n frames of the call ([n, ...]); after labelImage one frame."""
+    _destroy = "kde_les_destroy"
+
+    def __init__(self, width: int, height: int, max_batch: int = 1, params: Optional[LesParams] = None):
+        super().__init__()
+        self.width, self.height, self.max_batch = width, height, max_batch
+        self._n, self._k = 1, 0
+        check(lib().kde_les_create(C.byref(self._h), width, height, max_batch, C.byref(params) if params is not None else None))
+
+    @staticmethod
+    def default_params() -> LesParams:
+        p = LesParams()
+        check(lib().kde_les_default_params(C.byref(p)))
+        return p
+
+    def labelImage(self, cluster_normals_device: torch.Tensor, cluster_label_device: torch.Tensor,
+                   cluster_centers_device: torch.Tensor, variance_device: Optional[torch.Tensor] = None) -> None:
+        """LabelEquivalenceSeg.cu:228-282; variance_device is dead in the reference and never read"""
+        if not isinstance(cluster_normals_device, torch.Tensor) or cluster_normals_device.dim() != 2:
+            raise ValueError("cluster_normals_device: expected a [k, 3] tensor")
+        k = cluster_normals_device.shape[0]
+        _req(cluster_normals_device, torch.float32, (k, 3), "cluster_normals_device")
+        _req(cluster_label_device, torch.int32, (self.height, self.width), "cluster_label_device")
+        _req(cluster_centers_device, torch.float32, (k, 3), "cluster_centers_device")
+        check(lib().kde_les_label_image(self._h, cluster_normals_device.data_ptr(), cluster_label_device.data_ptr(),
+                                        cluster_centers_device.data_ptr(), _ptr(variance_device), k, _stream()))
+        self._n, self._k = 1, k
+
+    def label_image_batch(self, normals: torch.Tensor, labels: torch.Tensor, centers: torch.Tensor,
+                          variance: Optional[torch.Tensor] = None) -> None:
+        """n independent frames back to back ([n, k, 3], [n, H, W], [n, k, 3]); each frame's result is bit-identical to its
+        labelImage"""
+        if not isinstance(normals, torch.Tensor) or normals.dim() != 3:
+            raise ValueError("normals: expected a [n, k, 3] tensor")
+        n, k = normals.shape[0], normals.shape[1]
+        _req(normals, torch.float32, (n, k, 3), "normals")
+        _req(labels, torch.int32, (n, self.height, self.width), "labels")
+        _req(centers, torch.float32, (n, k, 3), "centers")
+        check(lib().kde_les_label_image_batch(self._h, n, normals.data_ptr(), labels.data_ptr(), centers.data_ptr(),
+                                              _ptr(variance), k, _stream()))
+        self._n, self._k = n, k
+
+    def _lead(self):
+        return () if self._n == 1 else (self._n,)
+
+    def _get(self, fn, shape, dtype):
+        p = C.c_void_p()
+        check(getattr(lib(), fn)(self._h, C.byref(p)))
+        return _view(p.value, self._lead() + tuple(shape), dtype, self)
+
+    def getMergedClusterLabel_Device(self) -> torch.Tensor:
+        return self._get("kde_les_merged_label_device", (self.height, self.width), torch.int32)
+
+    def getMergedClusterND_Device(self) -> torch.Tensor:
+        return self._get("kde_les_merged_nd_device", (self.height, self.width, 4), torch.float32)
+
+    def getMergedClusterVariance_Device(self) -> torch.Tensor:
+        """indexed by merged label, one entry per superpixel of the last call"""
+        return self._get("kde_les_merged_variance_device", (self._k,), torch.float32)
+
+    def getMergedClusterSize_Device(self) -> torch.Tensor:
+        """indexed by merged label, one entry per superpixel of the last call"""
+        return self._get("kde_les_merged_size_device", (self._k,), torch.int32)
+
+    def getMergedClusterLabel_Host(self) -> np.ndarray:
+        p = C.c_void_p()
+        check(lib().kde_les_merged_label_host(self._h, _stream(), C.byref(p)))
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_int32)), shape=self._lead() + (self.height, self.width)).copy()
+
+    def getMergedClusterND_Host(self) -> np.ndarray:
+        p = C.c_void_p()
+        check(lib().kde_les_merged_nd_host(self._h, _stream(), C.byref(p)))
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_float)), shape=self._lead() + (self.height, self.width, 4)).copy()
+
+    def getNormalImg(self) -> np.ndarray:
+        """LabelEquivalenceSeg.cpp:109-124: per pixel its region's normal as (unsigned char)(255*(n+1)/2), black where
+        the merged label is -1"""
+        labels, nd = self.getMergedClusterLabel_Host(), self.getMergedClusterND_Host()
+        v = np.float32(255.0) * (nd[..., :3] + np.float32(1.0)) / np.float32(2.0)
+        v = np.where(np.isfinite(v), v, 0.0)
+        img = (np.clip(np.trunc(v), -2147483648, 2147483647).astype(np.int64) & 0xFF).astype(np.uint8)
+        return np.where((labels > -1)[..., None], img, 0).astype(np.uint8)
+
+    def getSegmentResult(self) -> np.ndarray:
+        """LabelEquivalenceSeg.cpp:87-108: one colour per merged label from a fixed-seed palette (the reference
+        draws them with rand()), black where the merged label is -1"""
+        labels = self.getMergedClusterLabel_Host()
+        palette = np.random.default_rng(12345).integers(0, 256, (max(self._k, 1), 3)).astype(np.uint8)
+        return np.where((labels > -1)[..., None], palette[np.clip(labels, 0, max(self._k, 1) - 1)], 0).astype(np.uint8)
 
 
 class EdgeRefinedSuperpixel(_Handle):
