@@ -11,6 +11,8 @@
 //   RegionGrowingBilateralFilter(RegionGrowingBilateralFilter.h:11-27)
 //   SPDepthSuperResolution      (SPDepthSuperResolution.h:17-46)
 //   LabelEquivalenceSeg         (LabelEquivalenceSeg/LabelEquivalenceSeg.h:7-49)
+//   Projection_GPU              (Projection_GPU/Projection_GPU.h:8-42; the five-argument PlaneProjection)
+//   KinectDepthEnhancement      (KinectDepthEnhancement.h:19-44)
 //   kde::JointBilateralFilterFeed (extension: JointBilateralFilter on frames in host memory, main.cpp:160-163)
 //
 // What differs from the reference headers, and why:
@@ -855,6 +857,132 @@ private:
     HostImage8UC3 show, normalImage;
 };
 
+// ------------------------------------------------------------------------------------------------
+// Projection_GPU/Projection_GPU.h:8-42, the five-argument PlaneProjection (kde_proj_*): the consumer of LabelEquivalenceSeg's
+// four outputs in KinectDepthEnhancement.cpp:79-80.  The reference class cannot know how long the variance and size
+// tables are; here setClusterCount() says it (rows * cols of the segmentation) before the first PlaneProjection.  The
+// three-argument overload runs inside SPDepthSuperResolution::Process; the float3-normals overload has no caller.
+class Projection_GPU {
+public:
+    static constexpr int WindowSize = 7;            // Projection_GPU.cpp:3-5
+    static constexpr float SpatialSigma = 20.0f;
+    static constexpr float DepthSigma = 100.0f;
+    template <class MatLike>
+    Projection_GPU(int width, int height, const MatLike& intrinsic) : Width(width), Height(height)
+    {
+        double k[9];
+        intrinsic_to_array(intrinsic, k);
+        check(kde_proj_create(&h_, width, height, 1, k, nullptr));
+    }
+    ~Projection_GPU() { kde_proj_destroy(h_); }
+    Projection_GPU(const Projection_GPU&) = delete;
+    Projection_GPU& operator=(const Projection_GPU&) = delete;
+
+    void setClusterCount(int n_clusters) { Clusters = n_clusters; }   // added: the length of the variance and size tables
+    // Projection_GPU.cu:248-272
+    void PlaneProjection(const float4* nd_device, const int* labels_device, const float* variance_device, const float3* points3d_device,
+                         int* size_device)
+    {
+        check(kde_proj_plane_projection(h_, reinterpret_cast<const kde_float4*>(nd_device), labels_device, variance_device,
+                                        reinterpret_cast<const kde_float3*>(points3d_device), size_device, Clusters, stream_));
+    }
+    float3* GetPlaneFitted3D_Device() const
+    {
+        kde_float3* p = nullptr;
+        check(kde_proj_plane_fitted_points_device(h_, &p));
+        return reinterpret_cast<float3*>(p);
+    }
+    float3* GetOptimized3D_Device() const
+    {
+        kde_float3* p = nullptr;
+        check(kde_proj_optimized_points_device(h_, &p));
+        return reinterpret_cast<float3*>(p);
+    }
+    // the *_Host members: object-owned pinned copies, refreshed by a blocking copy on the object's stream
+    float3* GetPlaneFitted3D_Host() const
+    {
+        const kde_float3* p = nullptr;
+        check(kde_proj_plane_fitted_points_host(h_, stream_, &p));
+        return reinterpret_cast<float3*>(const_cast<kde_float3*>(p));
+    }
+    float3* GetOptimized3D_Host() const
+    {
+        const kde_float3* p = nullptr;
+        check(kde_proj_optimized_points_host(h_, stream_, &p));
+        return reinterpret_cast<float3*>(const_cast<kde_float3*>(p));
+    }
+    void setStream(void* hip_stream) { stream_ = hip_stream; }
+    kde_proj* handle() const { return h_; }
+
+private:
+    int Width, Height, Clusters = 0;
+    kde_proj* h_ = nullptr;
+    void* stream_ = nullptr;
+};
+
+// ------------------------------------------------------------------------------------------------
+// KinectDepthEnhancement.h:19-44 (kde_enh_*): the "PROPOSED" method of main.cpp:198-202.  getRefinedDepth_Device / _Host
+// (.cpp:82-87) are not built: they return a buffer of the EdgeRefinedSuperpixel member that Process never writes.
+class KinectDepthEnhancement {
+public:
+    KinectDepthEnhancement(int width, int height) : Width(width), Height(height) { check(kde_enh_create(&h_, width, height, 1)); }
+    ~KinectDepthEnhancement() { kde_enh_destroy(h_); }
+    KinectDepthEnhancement(const KinectDepthEnhancement&) = delete;
+    KinectDepthEnhancement& operator=(const KinectDepthEnhancement&) = delete;
+
+    template <class MatLike>
+    void SetParametor(int rows, int cols, const MatLike& intrinsic)   // [sic], .cpp:46-55
+    {
+        double k[9];
+        intrinsic_to_array(intrinsic, k);
+        check(kde_enh_set_parameters(h_, rows, cols, k));
+    }
+    template <class GpuMatLike>
+    void Process(float* depth_device, const GpuMatLike& color_device)   // .cpp:56-81
+    {
+        require_continuous_8uc3(color_device, Width, Height, "KinectDepthEnhancement::Process");
+        check(kde_enh_process_batch(h_, 1, depth_device, color_device.data, stream_));
+    }
+    float3* getOptimizedPoints_Device()
+    {
+        kde_float3* p = nullptr;
+        check(kde_enh_optimized_points_device(h_, &p));
+        return reinterpret_cast<float3*>(p);
+    }
+    float3* getOptimizedPoints_Host()
+    {
+        const kde_float3* p = nullptr;
+        check(kde_enh_optimized_points_host(h_, stream_, &p));
+        return reinterpret_cast<float3*>(const_cast<kde_float3*>(p));
+    }
+    // added: the intermediate results a caller of the reference would read off the private members
+    int* getLabelDevice() const
+    {
+        int32_t* p = nullptr;
+        check(kde_enh_nasp_labels_device(h_, &p));
+        return p;
+    }
+    int* getMergedClusterLabel_Device() const
+    {
+        int32_t* p = nullptr;
+        check(kde_enh_merged_labels_device(h_, &p));
+        return p;
+    }
+    float3* getEdgeEnhanced3DPoints_Device() const
+    {
+        kde_float3* p = nullptr;
+        check(kde_enh_edge_enhanced_points_device(h_, &p));
+        return reinterpret_cast<float3*>(p);
+    }
+    void setStream(void* hip_stream) { stream_ = hip_stream; }
+    kde_enh* handle() const { return h_; }
+
+private:
+    int Width, Height;
+    kde_enh* h_ = nullptr;
+    void* stream_ = nullptr;
+};
+
 }  // namespace ref
 
 // ------------------------------------------------------------------------------------------------
@@ -899,10 +1027,12 @@ using kde::ref::DepthAdaptiveSuperpixel;
 using kde::ref::DimensionConvertor;
 using kde::ref::EdgeRefinedSuperpixel;
 using kde::ref::JointBilateralFilter;
+using kde::ref::KinectDepthEnhancement;
 using kde::ref::LabelEquivalenceSeg;
 using kde::ref::MarkovRandomField;
 using kde::ref::NormalAdaptiveSuperpixel;
 using kde::ref::NormalMapGenerator;
+using kde::ref::Projection_GPU;
 using kde::ref::RegionGrowingBilateralFilter;
 using kde::ref::SPDepthSuperResolution;
 #endif

@@ -455,6 +455,76 @@ int kde_les_merged_size_device(kde_les* h, int32_t** out);          /* getMerged
 int kde_les_merged_label_host(kde_les* h, void* stream, const int32_t** out);       /* getMergedClusterLabel_Host (.cpp:134) */
 int kde_les_merged_nd_host(kde_les* h, void* stream, const kde_float4** out);       /* getMergedClusterND_Host (.cpp:131)    */
 
+/* ============================================================================================
+ * Projection_GPU — Projection_GPU/Projection_GPU.{h,cpp,cu}, the five-argument PlaneProjection (.cu:248-272): every pixel
+ * of a region whose normals agree (acos(variance) < max_angle) is projected along its ray onto the region's plane; where
+ * the region is also larger than min_size and the projected depth is within 3 % of the measured one, the depth is replaced
+ * by (within 1 %) or blended with (by the variance) the projected one; a window_size^2 depth-bilateral filter smooths the
+ * result.  The consumer of LabelEquivalenceSeg's four outputs in KinectDepthEnhancement.cpp:79-80.  Batched, asynchronous
+ * on the caller's stream, capturable, no allocation and no host synchronisation after kde_proj_create.  Definition and the
+ * deviations P1-P5 are in DESIGN.md ("Plane projection (five-argument)"); the checker is tools/proj_ref.c.
+ * (kde_spdsr_* holds the three-argument overload, which runs inside SPDepthSuperResolution::Process.)
+ * ========================================================================================== */
+typedef struct kde_proj kde_proj;
+typedef struct kde_proj_params {
+    int   window_size;              /* WindowSize = 7      Projection_GPU.cpp:4  (odd, 1..15)                          */
+    float spatial_sigma;            /* SpatialSigma = 20   :3  (pixels, not 0 and not NaN)                             */
+    float depth_sigma;              /* DepthSigma = 100    :5  (millimetres, > 0)                                      */
+    float max_angle;                /* 3.141592653f / 8.0f radians   Projection_GPU.cu:38, :203                        */
+    int   min_size;                 /* 1300 pixels: a region counts as large when size > min_size   .cu:203            */
+} kde_proj_params;
+/* fills the reference's constants: 7, 20, 100, 3.141592653f / 8.0f, 1300 */
+int kde_proj_default_params(kde_proj_params* p);
+/* Projection_GPU(int width, int height, const cv::Mat intrinsic) (Projection_GPU.cpp:7-21): K9 is the row-major 3x3
+ * intrinsic matrix, Fx,Fy = (float)K00,K11; Cx,Cy = (int)K02,K12 (truncated).  Builds the unit-depth rays (initTemp,
+ * .cu:3-19) and the spatial table (calcSpatialFilter, .cpp:35-44) once.  params == NULL -> defaults; max_batch >= 1 sizes
+ * the object-owned buffers. */
+int kde_proj_create(kde_proj** out, int width, int height, int max_batch, const double* K9, const kde_proj_params* params);
+int kde_proj_destroy(kde_proj* h);                                  /* ~Projection_GPU (.cpp:23-33) */
+/* void PlaneProjection(const float4* nd_device, const int* labels_device, const float* variance_device,
+ *                      const float3* points3d_device, int* size_device) (.cu:248-272).  nd and labels are per pixel,
+ * variance and size are tables of n_clusters >= 1 entries indexed by label: what the four kde_les_merged_*_device getters
+ * return.  A label outside [0, n_clusters) is a pixel without region. */
+int kde_proj_plane_projection(kde_proj* h, const kde_float4* nd_dev, const int32_t* labels_dev, const float* variance_dev,
+                              const kde_float3* points_dev, const int32_t* size_dev, int n_clusters, void* stream);
+/* the same over n <= max_batch frames back to back: per-pixel inputs [n][H][W], tables [n][n_clusters]; frame f's result is
+ * bit-identical to its single-frame call */
+int kde_proj_plane_projection_batch(kde_proj* h, int n, const kde_float4* nd_dev, const int32_t* labels_dev,
+                                    const float* variance_dev, const kde_float3* points_dev, const int32_t* size_dev,
+                                    int n_clusters, void* stream);
+/* object-owned, the frames of the last call back to back; the host copies are pinned and refreshed lazily by a blocking
+ * copy on `stream` (the reference's copies are commented out, .cu:269-270): the only calls that synchronise */
+int kde_proj_optimized_points_device(kde_proj* h, kde_float3** out);                        /* GetOptimized3D_Device (.cpp:62-64)   */
+int kde_proj_optimized_points_host(kde_proj* h, void* stream, const kde_float3** out);      /* GetOptimized3D_Host (:59-61)         */
+int kde_proj_plane_fitted_points_device(kde_proj* h, kde_float3** out);                     /* GetPlaneFitted3D_Device (:56-58)     */
+int kde_proj_plane_fitted_points_host(kde_proj* h, void* stream, const kde_float3** out);   /* GetPlaneFitted3D_Host (:52-54)       */
+
+/* ============================================================================================
+ * KinectDepthEnhancement — KinectDepthEnhancement.{h,cpp}: the reference's "PROPOSED" method (main.cpp:198-202).
+ * Process = .cpp:56-81: JointBilateralFilter (defaults), projectiveToReal(float*), NormalMapGenerator (CM),
+ * NormalAdaptiveSuperpixel::Segmentation(10, 50, 50, 150, 1), LabelEquivalenceSeg::labelImage with rows*cols superpixels
+ * and the five-argument PlaneProjection (defaults).  Composition only: every stage is the object above, and each output
+ * is bit-identical to the six stage objects called by hand.  Not built: the two cv::imwrite calls (:69, :77), and
+ * getRefinedDepth_Device / _Host (:82-87), which return a buffer of the EdgeRefinedSuperpixel member that Process never
+ * writes.
+ * ========================================================================================== */
+typedef struct kde_enh kde_enh;
+/* KinectDepthEnhancement(int width, int height) (.cpp:11-24); max_batch >= 1 sizes every stage */
+int kde_enh_create(kde_enh** out, int width, int height, int max_batch);
+int kde_enh_destroy(kde_enh* h);                                    /* ~KinectDepthEnhancement (.cpp:25-45) */
+/* void SetParametor(int rows, int cols, cv::Mat_<double> intrinsic) (.cpp:46-55).  Refuses what kde_nasp_set_parameters
+ * refuses, and rows*cols > min(W*H, 2048), the kde_les_label_image bound.  Builds NormalAdaptiveSuperpixel's weight tables
+ * for Process's sigmas, so kde_enh_process_batch can be captured from the first call. */
+int kde_enh_set_parameters(kde_enh* h, int rows, int cols, const double* K9);
+/* void Process(float* depth_device, cv::gpu::GpuMat color_device) (.cpp:56-81) over n <= max_batch frames back to back */
+int kde_enh_process_batch(kde_enh* h, int n, const float* depth_dev, const uint8_t* bgr_dev, void* stream);
+/* object-owned, the frames of the last call back to back */
+int kde_enh_optimized_points_device(kde_enh* h, kde_float3** out);                          /* getOptimizedPoints_Device (.cpp:88-90) */
+int kde_enh_optimized_points_host(kde_enh* h, void* stream, const kde_float3** out);        /* getOptimizedPoints_Host (:91-93)       */
+int kde_enh_nasp_labels_device(kde_enh* h, int32_t** out);          /* NASP->getLabelDevice()                       */
+int kde_enh_merged_labels_device(kde_enh* h, int32_t** out);        /* spMerging->getMergedClusterLabel_Device()    */
+int kde_enh_edge_enhanced_points_device(kde_enh* h, kde_float3** out);   /* EdgeEnhanced3DPoints_Device             */
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,6 +43,12 @@ class LesParams(C.Structure):
     _fields_ = [("iterations", C.c_int), ("max_angle", C.c_float), ("max_plane_distance", C.c_float)]
 
 
+class ProjParams(C.Structure):
+    """kde_proj_params (defaults = Projection_GPU.cpp:3-5, Projection_GPU.cu:38, :203)."""
+    _fields_ = [("window_size", C.c_int), ("spatial_sigma", C.c_float), ("depth_sigma", C.c_float), ("max_angle", C.c_float),
+                ("min_size", C.c_int)]
+
+
 class FeedStats(C.Structure):
     """kde_feed_stats: what the last kde_jbf_feed_process call did."""
     _fields_ = [("frames", C.c_int), ("chunks", C.c_int), ("chunk_frames", C.c_int), ("inputs_staged", C.c_int),
@@ -190,6 +196,24 @@ SIGNATURES = {
     "kde_les_merged_size_device": (_i, [_vp, _pp]),
     "kde_les_merged_label_host": (_i, [_vp, _vp, _pp]),
     "kde_les_merged_nd_host": (_i, [_vp, _vp, _pp]),
+    "kde_proj_default_params": (_i, [C.POINTER(ProjParams)]),
+    "kde_proj_create": (_i, [_pp, _i, _i, _i, _vp, C.POINTER(ProjParams)]),
+    "kde_proj_destroy": (_i, [_vp]),
+    "kde_proj_plane_projection": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "kde_proj_plane_projection_batch": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "kde_proj_optimized_points_device": (_i, [_vp, _pp]),
+    "kde_proj_optimized_points_host": (_i, [_vp, _vp, _pp]),
+    "kde_proj_plane_fitted_points_device": (_i, [_vp, _pp]),
+    "kde_proj_plane_fitted_points_host": (_i, [_vp, _vp, _pp]),
+    "kde_enh_create": (_i, [_pp, _i, _i, _i]),
+    "kde_enh_destroy": (_i, [_vp]),
+    "kde_enh_set_parameters": (_i, [_vp, _i, _i, _vp]),
+    "kde_enh_process_batch": (_i, [_vp, _i, _vp, _vp, _vp]),
+    "kde_enh_optimized_points_device": (_i, [_vp, _pp]),
+    "kde_enh_optimized_points_host": (_i, [_vp, _vp, _pp]),
+    "kde_enh_nasp_labels_device": (_i, [_vp, _pp]),
+    "kde_enh_merged_labels_device": (_i, [_vp, _pp]),
+    "kde_enh_edge_enhanced_points_device": (_i, [_vp, _pp]),
 }
 
 

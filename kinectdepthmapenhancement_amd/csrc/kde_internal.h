@@ -254,6 +254,28 @@ struct LesLaunch {
 };
 int launch_les_label_image(const LesLaunch& a, hipStream_t s);   // 3 kernels
 
+// Projection_GPU::PlaneProjection, five-argument overload (proj_kernels.hip): n frames back to back; the two tables are
+// strided by nc, the rays and the spatial table belong to the camera / the handle
+constexpr int kProjMaxWindow = 15;
+struct ProjLaunch {
+    int width, height, n;
+    int nc;                        // entries per frame of variance / size (P1)
+    const float4* nd;              // [n][H][W] merged (n, d) per pixel
+    const int32_t* labels;         // [n][H][W] merged label
+    const float* variance;         // [n][nc] by merged label
+    const kde_float3* pts;         // [n][H][W] millimetres
+    const int32_t* size;           // [n][nc] by merged label
+    const float2* nxy;             // [H][W] x, y of the unit-depth ray (initTemp)
+    const float* spatial;          // window^2 (calcSpatialFilter)
+    kde_float3* plane_fitted;      // [n][H][W]
+    float* z;                      // [n][H][W] z as variance_optimization leaves it
+    kde_float3* optimized;         // [n][H][W]
+    int window, min_size;
+    float thr;                     // P3: the L6 threshold of max_angle
+    float depth_den;               // 2 * depth_sigma^2 as .cu:231 forms it
+};
+int launch_proj_plane_projection(const ProjLaunch& a, hipStream_t s);   // 2 kernels
+
 int launch_ers_edge_phase(int width, int height, int dir, int window, const int32_t* color_labels, const int32_t* l0,
                           const float* d0, int32_t* l1, float* d1, hipStream_t s);
 int launch_ers_edge_refining(int width, int height, int n, int window, const int32_t* color_labels, const int32_t* l0,

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _native
-from ._native import JbfParams, LesParams, NormalsParams, check, lib
+from ._native import JbfParams, LesParams, NormalsParams, ProjParams, check, lib
 
 
 def _stream() -> int:
@@ -641,6 +641,142 @@ class LabelEquivalenceSeg(_Handle):
         labels = self.getMergedClusterLabel_Host()
         palette = np.random.default_rng(12345).integers(0, 256, (max(self._k, 1), 3)).astype(np.uint8)
         return np.where((labels > -1)[..., None], palette[np.clip(labels, 0, max(self._k, 1) - 1)], 0).astype(np.uint8)
+
+
+class PlaneProjection(_Handle):
+    """Projection_GPU/Projection_GPU.h, the five-argument PlaneProjection: projects every pixel of an agreeing region onto
+    the region's plane, replaces or blends the measured depth where the two are close and the region is large, and smooths
+    with a depth-bilateral filter.  Takes what LabelEquivalenceSeg's four *_Device getters return.  After
+    plane_projection_batch the getters return the n frames of the call ([n, ...]); after PlaneProjection one frame."""
+    _destroy = "kde_proj_destroy"
+
+    def __init__(self, width: int, height: int, intrinsic, max_batch: int = 1, params: Optional[ProjParams] = None):
+        super().__init__()
+        self.width, self.height, self.max_batch = width, height, max_batch
+        self._n = 1
+        k = _K9(intrinsic)
+        check(lib().kde_proj_create(C.byref(self._h), width, height, max_batch, k.ctypes.data,
+                                    C.byref(params) if params is not None else None))
+
+    @staticmethod
+    def default_params() -> ProjParams:
+        p = ProjParams()
+        check(lib().kde_proj_default_params(C.byref(p)))
+        return p
+
+    def PlaneProjection(self, nd_device: torch.Tensor, labels_device: torch.Tensor, variance_device: torch.Tensor,
+                        points3d_device: torch.Tensor, size_device: torch.Tensor) -> None:
+        """Projection_GPU.cu:248-272; the number of table entries is the length of variance_device"""
+        if not isinstance(variance_device, torch.Tensor) or variance_device.dim() != 1:
+            raise ValueError("variance_device: expected a [k] tensor")
+        k, hw = variance_device.shape[0], (self.height, self.width)
+        _req(nd_device, torch.float32, hw + (4,), "nd_device")
+        _req(labels_device, torch.int32, hw, "labels_device")
+        _req(variance_device, torch.float32, (k,), "variance_device")
+        _req(points3d_device, torch.float32, hw + (3,), "points3d_device")
+        _req(size_device, torch.int32, (k,), "size_device")
+        check(lib().kde_proj_plane_projection(self._h, nd_device.data_ptr(), labels_device.data_ptr(), variance_device.data_ptr(),
+                                              points3d_device.data_ptr(), size_device.data_ptr(), k, _stream()))
+        self._n = 1
+
+    def plane_projection_batch(self, nd: torch.Tensor, labels: torch.Tensor, variance: torch.Tensor, points: torch.Tensor,
+                               size: torch.Tensor) -> None:
+        """n independent frames back to back ([n, H, W, 4], [n, H, W], [n, k], [n, H, W, 3], [n, k]); each frame's result is
+        bit-identical to its PlaneProjection"""
+        if not isinstance(variance, torch.Tensor) or variance.dim() != 2:
+            raise ValueError("variance: expected a [n, k] tensor")
+        n, k = variance.shape
+        hw = (self.height, self.width)
+        _req(nd, torch.float32, (n,) + hw + (4,), "nd")
+        _req(labels, torch.int32, (n,) + hw, "labels")
+        _req(variance, torch.float32, (n, k), "variance")
+        _req(points, torch.float32, (n,) + hw + (3,), "points")
+        _req(size, torch.int32, (n, k), "size")
+        check(lib().kde_proj_plane_projection_batch(self._h, n, nd.data_ptr(), labels.data_ptr(), variance.data_ptr(),
+                                                    points.data_ptr(), size.data_ptr(), k, _stream()))
+        self._n = n
+
+    def _lead(self):
+        return () if self._n == 1 else (self._n,)
+
+    def _device(self, fn):
+        p = C.c_void_p()
+        check(getattr(lib(), fn)(self._h, C.byref(p)))
+        return _view(p.value, self._lead() + (self.height, self.width, 3), torch.float32, self)
+
+    def _host(self, fn):
+        p = C.c_void_p()
+        check(getattr(lib(), fn)(self._h, _stream(), C.byref(p)))
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_float)), shape=self._lead() + (self.height, self.width, 3)).copy()
+
+    def GetOptimized3D_Device(self) -> torch.Tensor:
+        return self._device("kde_proj_optimized_points_device")
+
+    def GetOptimized3D_Host(self) -> np.ndarray:
+        return self._host("kde_proj_optimized_points_host")
+
+    def GetPlaneFitted3D_Device(self) -> torch.Tensor:
+        return self._device("kde_proj_plane_fitted_points_device")
+
+    def GetPlaneFitted3D_Host(self) -> np.ndarray:
+        return self._host("kde_proj_plane_fitted_points_host")
+
+
+class KinectDepthEnhancement(_Handle):
+    """KinectDepthEnhancement.h: the reference's "PROPOSED" method (main.cpp:198-202).  Process = JointBilateralFilter,
+    projectiveToReal, NormalMapGenerator (CM), NormalAdaptiveSuperpixel (10, 50, 50, 150, 1), LabelEquivalenceSeg and the
+    five-argument PlaneProjection (KinectDepthEnhancement.cpp:56-81).  getRefinedDepth_* is not built: it returns a buffer
+    Process never writes."""
+    _destroy = "kde_enh_destroy"
+
+    def __init__(self, width: int, height: int, max_batch: int = 1):
+        super().__init__()
+        self.width, self.height, self.max_batch = width, height, max_batch
+        self._n = 1
+        check(lib().kde_enh_create(C.byref(self._h), width, height, max_batch))
+
+    def SetParametor(self, rows: int, cols: int, intrinsic) -> None:
+        k = _K9(intrinsic)
+        check(lib().kde_enh_set_parameters(self._h, rows, cols, k.ctypes.data))
+
+    def Process(self, depth_device: torch.Tensor, color_device: torch.Tensor) -> None:
+        _req(depth_device, torch.float32, (self.height, self.width), "depth_device")
+        _req(color_device, torch.uint8, (self.height, self.width, 3), "color_device")
+        check(lib().kde_enh_process_batch(self._h, 1, depth_device.data_ptr(), color_device.data_ptr(), _stream()))
+        self._n = 1
+
+    def process_batch(self, depth: torch.Tensor, color: torch.Tensor) -> None:
+        """n independent frames back to back ([n, H, W] and [n, H, W, 3])"""
+        n = depth.shape[0]
+        _req(depth, torch.float32, (n, self.height, self.width), "depth")
+        _req(color, torch.uint8, (n, self.height, self.width, 3), "color")
+        check(lib().kde_enh_process_batch(self._h, n, depth.data_ptr(), color.data_ptr(), _stream()))
+        self._n = n
+
+    def _get(self, fn, trailing, dtype):
+        p = C.c_void_p()
+        check(getattr(lib(), fn)(self._h, C.byref(p)))
+        lead = () if self._n == 1 else (self._n,)
+        return _view(p.value, lead + (self.height, self.width) + trailing, dtype, self)
+
+    def getOptimizedPoints_Device(self) -> torch.Tensor:
+        return self._get("kde_enh_optimized_points_device", (3,), torch.float32)
+
+    def getOptimizedPoints_Host(self) -> np.ndarray:
+        p = C.c_void_p()
+        check(lib().kde_enh_optimized_points_host(self._h, _stream(), C.byref(p)))
+        lead = () if self._n == 1 else (self._n,)
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_float)), shape=lead + (self.height, self.width, 3)).copy()
+
+    def getLabelDevice(self) -> torch.Tensor:
+        """NASP->getLabelDevice(): the superpixel labels before merging"""
+        return self._get("kde_enh_nasp_labels_device", (), torch.int32)
+
+    def getMergedClusterLabel_Device(self) -> torch.Tensor:
+        return self._get("kde_enh_merged_labels_device", (), torch.int32)
+
+    def getEdgeEnhanced3DPoints_Device(self) -> torch.Tensor:
+        return self._get("kde_enh_edge_enhanced_points_device", (3,), torch.float32)
 
 
 class EdgeRefinedSuperpixel(_Handle):
