@@ -4,8 +4,9 @@
 // The kernel is VALU/transcendental-bound (2 exp per tap against 11 B/pixel of traffic), so the work
 // per (pixel, tap) is cut to the minimum the reference's semantics allow:
 //   * colour distance as |a|^2 + |b|^2 - 2 a.b with ONE v_dot4_u32_u8 per tap on packed BGRX; -|b|^2 is
-//     staged in LDS pre-biased so that (a.b << 1) + bias (one v_lshl_add_u32) IS the bit pattern of the
-//     float 2^23 + 2^18 - |b|^2 + 2 a.b, i.e. no int->float convert;
+//     staged in LDS pre-biased so that the integer result IS the bit pattern of a float, i.e. no int->float convert:
+//     scalar kernels (a.b << 1) + bias (one v_lshl_add_u32 per tap) = 2^23 + 2^18 - |b|^2 + 2 a.b; packed kernels take 2^23's
+//     bits as the dot product's accumulator and double + bias BOTH taps of a pair with one exact v_pk_fma_f32;
 //   * weights live in the log2 domain: arg1 = log2(S_ij) - kc*cd, arg2 = arg1 - kd*(d_q - avg)^2, one
 //     v_exp_f32 per tap and pass; pass-1 arguments stay in registers for pass 2 (windows <= 7);
 //   * taps that are invalid (depth <= 50 mm or outside the image) cost no branch or select: the scalar kernels
@@ -36,6 +37,9 @@ constexpr uint32_t kMagic = 0x4B000000u;      // float 2^23
 constexpr uint32_t kOff = 1u << 18;           // keeps 2 a.b - |b|^2 + kOff positive (|b|^2 <= 195075 < 2^18)
 constexpr uint32_t kInvalidBias = 0xFF000000u; // as a float: -1.7e38; as an unsigned int: above every valid code
 constexpr float kBiasF = 8388608.0f + 262144.0f;
+// packed kernels: bits of the float -(2^24 - 2^18); as the accumulator of dot4(c, c, .) it gives the bits of -(2^24 - 2^18 + |c|^2)
+// (2^23 <= 2^24 - 2^18 + |c|^2 < 2^24: the sum stays in the mantissa field of one binade)
+constexpr uint32_t kNegHBits = 0xCB7C0000u;
 constexpr double kScaleLog2 = 24.0;           // weights are summed at 2^24 scale (see the header comment)
 
 struct FastArgs {
@@ -246,9 +250,12 @@ __global__ __launch_bounds__(BX* BY) void jbf_fast_kernel(const FastArgs a)
 // The spatial weight costs nothing per tap: log2(S[i][j]) of the unit's two taps is the (SGPR-pair) addend of
 // the argument fma.
 // Per unit (= 2 taps), window 11, in 4-cycle issue slots (v_exp_f32 counts 2):
-//   pass 1: 2 v_dot4 + 2 v_lshl_add + 2 v_exp + 6 packed (-cd, mask, mask*kc, arg fma, 2 accumulating fma) = 14.3
-//   pass 2: the same argument (8) + 2 v_exp + 8 packed (d-avg, *sd, T2-t^2, mask, t*mask, arg fma, 2 acc.)   = 20.3
-// (the select form of the Q1 rules cost 17 + 24: profiles/r01_sweep_k1_clamp_form.log has the A/B.)
+//   pass 1: 2 v_dot4 + 2 v_exp + 7 packed (2 a.b + h, -cd, mask, mask*kc, arg fma, 2 accumulating fma)        = 13.3
+//   pass 2: the same argument (7) + 2 v_exp + 8 packed (d-avg, *sd, T2-t^2, mask, t*mask, arg fma, 2 acc.)   = 19.3
+// (the select form of the Q1 rules cost 17 + 24: profiles/r01_sweep_k1_clamp_form.log has the A/B.  Until the colour code
+//  took its packed-fma form each tap paid a v_lshl_add_u32 of its own, (a.b << 1) + bias: 14.3 + 20.3; in a tile without
+//  rules 10.64 + 13.64 instructions per unit became 9.73 + 12.73, EXPERIMENTS.md Part I item 12.)
+// The leftover unit's two biases sit in different pairs: two scalar v_fma_f32 instead of v_pk_mov_b32 + v_pk_fma_f32.
 // ---------------------------------------------------------------------------------------------------
 typedef float f2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u2 __attribute__((ext_vector_type(2)));
@@ -275,8 +282,20 @@ __device__ __forceinline__ f2 pk_mul_clamp(f2 a, f2 b)
 //  came out at 228 / 248 registers, 2 waves per SIMD)
 // CR = window rows whose pass-1 arguments are kept for pass 2: all of them with CACHE (the windows <= 7), none otherwise
 // (recomputed).  r05's partial form (0 < CR < WIN at windows 9..13) was measured slower and removed (EXPERIMENTS.md).
+// Window 5 with the arguments kept: at least 5 waves per SIMD (<= 96 VGPRs); without the bound the instances come out
+// between 88 and 99 registers, on either side of that allocation step.  (The window-11 default needs no bound: 96 VGPRs, 5
+// waves per SIMD; asking for 5 there, or for the step above at windows 11 / 13 with one pair per thread, made the
+// scheduler spill 12-40 bytes.)
+constexpr int pk_min_waves(int win, int np, bool cache, bool cskip, bool elide_on)
+{
+    if (win >= 23) return 3;
+    if (win == 5 && np == 1 && cache) return 5;
+    return 1;
+}
+
 template <int WIN, int NP, int BX, int BY, bool CACHE, bool CSKIP, bool VL, bool ELIDE_ON = true, int CR = (CACHE ? WIN : 0)>
-__global__ __launch_bounds__(BX* BY) __attribute__((amdgpu_waves_per_eu(WIN >= 23 ? 3 : 1))) void jbf_pk_kernel(const FastArgs a)
+__global__ __launch_bounds__(BX* BY) __attribute__((amdgpu_waves_per_eu(pk_min_waves(WIN, NP, CACHE, CSKIP, ELIDE_ON))))
+void jbf_pk_kernel(const FastArgs a)
 {
     static_assert(CR == (CACHE ? WIN : 0), "cached rows: all or none");
     constexpr int R = WIN / 2;
@@ -306,7 +325,7 @@ __global__ __launch_bounds__(BX* BY) __attribute__((amdgpu_waves_per_eu(WIN >= 2
     static_assert(RA >= R && P % 2 == 0 && (!VL || ((RA + S1) % 4 == 0 && TW % 4 == 0 && (SH != 0 || P % 4 == 0))), "tile geometry");
     __shared__ __attribute__((aligned(16))) float s_d[LH * P];
     __shared__ __attribute__((aligned(16))) uint32_t s_c[LH * P];
-    __shared__ __attribute__((aligned(16))) uint32_t s_n[LH * P];
+    __shared__ __attribute__((aligned(16))) float s_n[LH * P];            // h_q = -(2^24 - 2^18 + |b|^2), see unit_arg
 
     const unsigned nblk = gridDim.x;
     const unsigned lin = blockIdx.x;
@@ -371,7 +390,7 @@ __global__ __launch_bounds__(BX* BY) __attribute__((amdgpu_waves_per_eu(WIN >= 2
             const bool valid = d > 50.0f;
             s_d[i] = valid ? d : 0.0f;
             s_c[i] = c;
-            s_n[i] = (kMagic + kOff) - dot4(c, c, 0);
+            s_n[i] = __uint_as_float(dot4(c, c, kNegHBits));
             stat(valid ? d : 0.0f, c, inside);
         }
     }
@@ -402,19 +421,19 @@ __global__ __launch_bounds__(BX* BY) __attribute__((amdgpu_waves_per_eu(WIN >= 2
                 }
             }
         }
-        uint32_t nn[4];
+        float nn[4];
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             const bool valid = d[k] > 50.0f;
             d[k] = valid ? d[k] : 0.0f;
-            nn[k] = (kMagic + kOff) - dot4(c[k], c[k], 0);
+            nn[k] = __uint_as_float(dot4(c[k], c[k], kNegHBits));
             stat(d[k], c[k], gy >= 0 && gy < a.height && gx + k >= 0 && gx + k < a.width);
         }
         const int li = ly * P + 4 * gi + SH;
         if constexpr (SH == 0) {
             *reinterpret_cast<float4*>(&s_d[li]) = make_float4(d[0], d[1], d[2], d[3]);
             *reinterpret_cast<uint4*>(&s_c[li]) = make_uint4(c[0], c[1], c[2], c[3]);
-            *reinterpret_cast<uint4*>(&s_n[li]) = make_uint4(nn[0], nn[1], nn[2], nn[3]);
+            *reinterpret_cast<float4*>(&s_n[li]) = make_float4(nn[0], nn[1], nn[2], nn[3]);
         } else {
 #pragma unroll
             for (int k = 0; k < 4; k++) {
@@ -477,7 +496,7 @@ __global__ __launch_bounds__(BX* BY) __attribute__((amdgpu_waves_per_eu(WIN >= 2
     const int sx = SH + RA - R + tx * PX;  // LDS column of this thread's first window column (even)
 
     uint32_t cc[PX];
-    f2 negC[NP];          // -(2^23 + 2^18 + |a|^2): F + negC = -cd exactly (integers < 2^24)
+    f2 negC[NP];          // -(2^18 + |a|^2): w + negC = -cd exactly (integers < 2^24)
 #pragma unroll
     for (int pp = 0; pp < NP; pp++) {
 #pragma unroll
@@ -485,7 +504,7 @@ __global__ __launch_bounds__(BX* BY) __attribute__((amdgpu_waves_per_eu(WIN >= 2
             const int k = 2 * pp + h;
             cc[k] = s_c[(ty + R) * P + sx + R + k];
             const uint32_t na = dot4(cc[k], cc[k], 0);
-            negC[pp][h] = -(kBiasF + (float)na);
+            negC[pp][h] = -((float)kOff + (float)na);
         }
     }
 
@@ -505,21 +524,37 @@ __global__ __launch_bounds__(BX* BY) __attribute__((amdgpu_waves_per_eu(WIN >= 2
     const f2 kBig = bcast(0x1p100f);
 
     // argument (log2 domain, without the row factor) of S*cf for the two taps of unit u of pair pp
-    auto unit_arg = [&](auto cs_tag, const u2* cp, const u2* np, int pp, int i, int u) -> f2 {
+    auto unit_arg = [&](auto cs_tag, const u2* cp, const f2* np, int pp, int i, int u) -> f2 {
         constexpr bool CS = decltype(cs_tag)::value;
-        uint32_t c0, c1, n0, n1;
+        uint32_t c0, c1;
+        f2 hq;
         if (u <= HALF) {                       // straight
-            c0 = cp[pp + u].x; c1 = cp[pp + u].y; n0 = np[pp + u].x; n1 = np[pp + u].y;
+            c0 = cp[pp + u].x; c1 = cp[pp + u].y; hq = np[pp + u];
         } else if (u < WIN - 1) {              // swapped
             const int m = pp + (u - HALF);
-            c0 = cp[m].y; c1 = cp[m].x; n0 = np[m].y; n1 = np[m].x;
+            c0 = cp[m].y; c1 = cp[m].x; hq = __builtin_shufflevector(np[m], np[m], 1, 0);
         } else {                               // leftover
-            c0 = cp[pp].y; c1 = cp[pp + HALF].x; n0 = np[pp].y; n1 = np[pp + HALF].x;
+            c0 = cp[pp].y; c1 = cp[pp + HALF].x; hq = bcast(0.0f);   // (not used: two scalar fmas below)
         }
-        const uint32_t u0 = (dot4(c0, cc[2 * pp], 0) << 1) + n0;
-        const uint32_t u1 = (dot4(c1, cc[2 * pp + 1], 0) << 1) + n1;
-        // -cd exactly, then ONE rounding in the fma: a1 = log2(S[i][j]) - kc*cd
-        const f2 ncd = f2{__uint_as_float(u0), __uint_as_float(u1)} + negC[pp];
+        // the dot product's accumulator input adds 2^23's bit pattern: the result IS the float 2^23 + a.b (a.b < 2^18)
+        const f2 ab = f2{__uint_as_float(dot4(c0, cc[2 * pp], kMagic)), __uint_as_float(dot4(c1, cc[2 * pp + 1], kMagic))};
+        // w = 2 (2^23 + a.b) - (2^24 - 2^18 + |b|^2) = 2 a.b - |b|^2 + 2^18 for both taps in ONE packed fma: an integer in
+        // [67069, 652294], so its rounding changes nothing; w + negC = -cd exactly; then ONE rounding in the argument fma:
+        // a1 = log2(S[i][j]) - kc*cd
+        f2 w;
+        if (u == WIN - 1) {
+            // leftover: its two h_q sit in different pairs.  Two scalar fmas write the halves of the result pair directly; the
+            // packed form needs a v_pk_mov_b32 into a pair of its own first (same instruction count, two more live registers:
+            // 74 instead of 72 VGPRs at window 11 with one pair per thread).  The empty asm only keeps the vectoriser from
+            // re-packing them; it emits no instruction.
+            float w0 = __builtin_fmaf(ab.x, 2.0f, np[pp].y), w1 = __builtin_fmaf(ab.y, 2.0f, np[pp + HALF].x);
+            asm("" : "+v"(w0));
+            asm("" : "+v"(w1));
+            w = f2{w0, w1};
+        } else {
+            w = pk_fma(ab, bcast(2.0f), hq);
+        }
+        const f2 ncd = w + negC[pp];
         f2 lsj;
         if constexpr (WIN > 21) {
             // the device copy is read through the CONSTANT address space: never written while the kernel runs, wave-uniform
@@ -542,13 +577,14 @@ __global__ __launch_bounds__(BX* BY) __attribute__((amdgpu_waves_per_eu(WIN >= 2
     auto pass1_row = [&](auto cs_tag, auto keep_tag, int i) {
         constexpr bool KEEP = decltype(keep_tag)::value;
         f2 dp[SEGP], vp[SEGP];
-        u2 cp[SEGP], np[SEGP];
+        u2 cp[SEGP];
+        f2 np[SEGP];
         const int rb = (ty + i) * P + sx;
 #pragma unroll
         for (int m = 0; m < SEGP; m++) {
             dp[m] = ALIGNED ? *reinterpret_cast<const f2*>(&s_d[rb + 2 * m]) : f2{s_d[rb + 2 * m], s_d[rb + 2 * m + 1]};
             cp[m] = ALIGNED ? *reinterpret_cast<const u2*>(&s_c[rb + 2 * m]) : u2{s_c[rb + 2 * m], s_c[rb + 2 * m + 1]};
-            np[m] = ALIGNED ? *reinterpret_cast<const u2*>(&s_n[rb + 2 * m]) : u2{s_n[rb + 2 * m], s_n[rb + 2 * m + 1]};
+            np[m] = ALIGNED ? *reinterpret_cast<const f2*>(&s_n[rb + 2 * m]) : f2{s_n[rb + 2 * m], s_n[rb + 2 * m + 1]};
             vp[m] = pk_add_clamp(dp[m], dp[m]);      // 1 for a valid tap (d > 50), 0 for d == 0
         }
 #pragma unroll
@@ -569,7 +605,8 @@ __global__ __launch_bounds__(BX* BY) __attribute__((amdgpu_waves_per_eu(WIN >= 2
         constexpr bool DS = decltype(ds_tag)::value;
         constexpr bool KEEP = decltype(keep_tag)::value;
         f2 dp[SEGP], vp[SEGP];
-        u2 cp[SEGP], np[SEGP];
+        u2 cp[SEGP];
+        f2 np[SEGP];
         const int rb = (ty + i) * P + sx;
 #pragma unroll
         for (int m = 0; m < SEGP; m++) {
@@ -577,7 +614,7 @@ __global__ __launch_bounds__(BX* BY) __attribute__((amdgpu_waves_per_eu(WIN >= 2
             vp[m] = pk_add_clamp(dp[m], dp[m]);
             if constexpr (!KEEP) {
                 cp[m] = ALIGNED ? *reinterpret_cast<const u2*>(&s_c[rb + 2 * m]) : u2{s_c[rb + 2 * m], s_c[rb + 2 * m + 1]};
-                np[m] = ALIGNED ? *reinterpret_cast<const u2*>(&s_n[rb + 2 * m]) : u2{s_n[rb + 2 * m], s_n[rb + 2 * m + 1]};
+                np[m] = ALIGNED ? *reinterpret_cast<const f2*>(&s_n[rb + 2 * m]) : f2{s_n[rb + 2 * m], s_n[rb + 2 * m + 1]};
             }
         }
 #pragma unroll
