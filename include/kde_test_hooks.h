@@ -47,10 +47,10 @@ int kde_test_fastdiv24(uint32_t d, uint64_t max_dividend, uint32_t n, const uint
  *   ers_avg   device float[H*W] or NULL: K10's label-restricted average (EdgeRefinedSuperpixel.cu:139-141)
  *   ers_dev   device float[H*W] or NULL: K10's mean absolute deviation (EdgeRefinedSuperpixel.cu:143-156); only
  *             meaningful where ers_avg is not NaN
- *   counters  device unsigned[8] or NULL, incremented once per tile: [0..3] K1 packed kernels by the body the tile ran
- *             (bit 0: colour rule compiled in, bit 1: depth rule), [4]/[5] K10 tiles with / without the "adaptive
+ *   counters  device unsigned[8] or NULL: [0..3] K1 packed kernels, once per wavefront that owns at least one pixel, by the
+ *             body the wavefront ran (bit 0: colour rule compiled in, bit 1: depth rule); once per tile: [4]/[5] K10 tiles with / without the "adaptive
  *             sigma provably small" shortcut, [6]/[7] K10 tiles without / with the depth rule in the colour-free rows
- *   force_full_rules  != 0: no tile-level elision — every tile runs the body with both Q1 rules (K1) / the per-pixel
+ *   force_full_rules  != 0: no rule elision — every wavefront runs the body with both Q1 rules (K1) / every tile the per-pixel
  *             deviation pass and the depth rule (K10); the output must not change by a bit                          */
 int kde_stage_set(float* jbf_avg_dev, float* ers_avg_dev, float* ers_dev_dev, unsigned* counters_dev, int force_full_rules);
 

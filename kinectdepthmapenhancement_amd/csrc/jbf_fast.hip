@@ -276,6 +276,37 @@ __device__ __forceinline__ f2 pk_mul_clamp(f2 a, f2 b)
     return r;
 }
 
+// packed 16-bit minimum / maximum (v_pk_min_u16 / v_pk_max_u16) on the two halves of a dword
+typedef unsigned short us2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t pk_min_u16(uint32_t a, uint32_t b)
+{
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(us2, a), __builtin_bit_cast(us2, b)));
+}
+__device__ __forceinline__ uint32_t pk_max_u16(uint32_t a, uint32_t b)
+{
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(us2, a), __builtin_bit_cast(us2, b)));
+}
+// Reduction of an idempotent, commutative op (min / max) over the 64 lanes of a wavefront with DPP moves, one per step:
+// lanes 1 and 2 apart inside every quad, quads 1 and 2 apart inside every row of 16 (row_ror), then row_bcast:15 into rows 1
+// and 3 and row_bcast:31 into rows 2 and 3 -- lane 63 holds the result, returned in a scalar register.  A lane the move does
+// not write keeps its own value (op(v, v) = v).  All 64 lanes must be active.
+template <int CTRL, int ROWS = 0xf>
+__device__ __forceinline__ uint32_t dpp_mov(uint32_t v)
+{
+    return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, ROWS, 0xf, false);
+}
+template <class Op>
+__device__ __forceinline__ uint32_t wave_reduce(uint32_t v, Op op)
+{
+    v = op(v, dpp_mov<0xb1>(v));           // quad_perm:[1,0,3,2]
+    v = op(v, dpp_mov<0x4e>(v));           // quad_perm:[2,3,0,1]
+    v = op(v, dpp_mov<0x124>(v));          // row_ror:4
+    v = op(v, dpp_mov<0x128>(v));          // row_ror:8
+    v = op(v, dpp_mov<0x142, 0xa>(v));     // row_bcast:15
+    v = op(v, dpp_mov<0x143, 0xc>(v));     // row_bcast:31
+    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+}
+
 // second launch bound = waves per SIMD the register allocator must leave room for: the four rule-specialised bodies
 // below share one kernel, and without it the window-19 instance grew from 131 to 182 VGPRs (3 -> 2 waves per SIMD)
 // (windows >= 23: at least 3 waves per SIMD, i.e. <= 168 VGPRs -- without the bound the instances without the colour rule
@@ -290,17 +321,27 @@ constexpr int pk_min_waves(int win, int np, bool cache, bool cskip, bool elide_o
 {
     if (win >= 23) return 3;
     if (win == 5 && np == 1 && cache) return 5;
+    // one pair per thread, no colour rule, rule body chosen per wavefront: without a bound the two bodies' schedules come out 20-34
+    // registers above the same instances with the colour rule (82 / 92 / 106 / 116 VGPRs at windows 9 / 11 / 13 / 15); window 11
+    // spills 28-32 bytes when asked for the 7 waves it had and takes 6 (74-76 VGPRs), like its twins with the colour rule
+    if (np == 1 && !cskip && elide_on && !cache && win >= 9 && win <= 15) return win == 9 ? 8 : win == 11 ? 6 : 5;
     return 1;
 }
 
-template <int WIN, int NP, int BX, int BY, bool CACHE, bool CSKIP, bool VL, bool ELIDE_ON = true, int CR = (CACHE ? WIN : 0)>
+// WTX = threads of one wavefront along x: a wavefront owns WTX x (64 / WTX) threads = (WTX * 2 NP) x (64 / WTX) pixels of the
+// tile.  WTX = BX is the plain row-major mapping (16x16 threads, two pairs each: 64x4 pixels per wavefront); WTX = 8 makes the
+// wavefronts 8x8 threads (32x8 pixels at two pairs per thread), the squarer footprint the per-wavefront rule elision below
+// wants (the window-11 built-in kernel; a tile BX = 8 threads wide has that footprint by itself).
+template <int WIN, int NP, int BX, int BY, bool CACHE, bool CSKIP, bool VL, bool ELIDE_ON = true, int WTX = BX>
 __global__ __launch_bounds__(BX* BY) __attribute__((amdgpu_waves_per_eu(pk_min_waves(WIN, NP, CACHE, CSKIP, ELIDE_ON))))
 void jbf_pk_kernel(const FastArgs a)
 {
-    static_assert(CR == (CACHE ? WIN : 0), "cached rows: all or none");
+    constexpr int CR = CACHE ? WIN : 0;      // cached rows: all or none
     constexpr int R = WIN / 2;
     constexpr int PX = 2 * NP;
     constexpr int NT = BX * BY;
+    constexpr int WTY = 64 / WTX, WAVES_X = BX / WTX;
+    static_assert(NT % 64 == 0 && 64 % WTX == 0 && BX % WTX == 0 && BY % WTY == 0, "whole wavefronts, each a WTX x WTY block of threads");
     constexpr int TW = BX * PX, TH = BY;
     constexpr int LH = TH + 2 * R;
     // LDS column 0 is image column o = xb0 - RA with xb0 = (tile index)*TW - S1.  S1 shifts the tiles one
@@ -344,35 +385,12 @@ void jbf_pk_kernel(const FastArgs a)
     const uint8_t* __restrict__ guide = a.guide + frame * 3;
     const int tid = threadIdx.x;
 
-    // Tile statistics for the rule elision below: range of the valid depths and per-channel range of the colours of
-    // the in-image pixels this workgroup stages (tile + halo = every tap and every centre the workgroup can see).
-    // Positive floats order like their bit patterns, so everything is reduced as uint32.
+    // ELIDE: windows >= 9 pick their rule body per wavefront (below, after the staging barrier).
     // (Only for windows >= 9: at windows 5 and 7 a thread has 25 / 49 units of work and the statistics cost more than
     //  the elided instructions return -- measured 33.9 vs 28.8 us on one 1080p frame at window 5.)
     // ELIDE_ON = false ("-noelide" variants): the same kernel without the statistics and with the full-rule body everywhere --
     // the data-independent floor of the window, measured next to the default by bench.py
     constexpr bool ELIDE = WIN >= 9 && ELIDE_ON;
-    __shared__ uint32_t s_stat[8];           // dmin, dmax, (min, max) of b, g, r
-    if (ELIDE) {
-        if (tid < 8) s_stat[tid] = (tid == 0 || (tid >= 2 && !(tid & 1))) ? 0xffffffffu : 0u;
-        __syncthreads();                     // the initial values are in place before any wavefront's atomics below
-    }
-    uint32_t st_dmin = 0x7f800000u, st_dmax = 0u, st_cmin[3] = {255u, 255u, 255u}, st_cmax[3] = {0u, 0u, 0u};
-    auto stat = [&](float dv, uint32_t c, bool inside) {        // dv: staged depth (0 = invalid)
-        if (!ELIDE) return;
-        if (dv > 0.0f) {
-            st_dmin = min(st_dmin, __float_as_uint(dv));
-            st_dmax = max(st_dmax, __float_as_uint(dv));
-        }
-        if (inside) {
-#pragma unroll
-            for (int ch = 0; ch < 3; ch++) {
-                const uint32_t v = (c >> (8 * ch)) & 0xffu;
-                st_cmin[ch] = min(st_cmin[ch], v);
-                st_cmax[ch] = max(st_cmax[ch], v);
-            }
-        }
-    };
 
     if (!VL) {
         for (int i = tid; i < P * LH; i += NT) {
@@ -391,7 +409,6 @@ void jbf_pk_kernel(const FastArgs a)
             s_d[i] = valid ? d : 0.0f;
             s_c[i] = c;
             s_n[i] = __uint_as_float(dot4(c, c, kNegHBits));
-            stat(valid ? d : 0.0f, c, inside);
         }
     }
     for (int g = tid; VL && g < G * LH; g += NT) {
@@ -427,7 +444,6 @@ void jbf_pk_kernel(const FastArgs a)
             const bool valid = d[k] > 50.0f;
             d[k] = valid ? d[k] : 0.0f;
             nn[k] = __uint_as_float(dot4(c[k], c[k], kNegHBits));
-            stat(d[k], c[k], gy >= 0 && gy < a.height && gx + k >= 0 && gx + k < a.width);
         }
         const int li = ly * P + 4 * gi + SH;
         if constexpr (SH == 0) {
@@ -443,46 +459,101 @@ void jbf_pk_kernel(const FastArgs a)
             }
         }
     }
-    if (ELIDE) {   // wavefront reduction (xor butterflies), then one LDS atomic per wavefront and statistic
-        uint32_t v[8] = {st_dmin, st_dmax, st_cmin[0], st_cmax[0], st_cmin[1], st_cmax[1], st_cmin[2], st_cmax[2]};
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-#pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) {
-                const uint32_t ov = (uint32_t)__shfl_xor((int)v[k], m, 64);
-                v[k] = (k & 1) ? max(v[k], ov) : min(v[k], ov);
-            }
-        }
-        if ((tid & 63) == 0) {
-#pragma unroll
-            for (int k = 0; k < 8; k++) {
-                if (k & 1) atomicMax(&s_stat[k], v[k]);
-                else atomicMin(&s_stat[k], v[k]);
-            }
-        }
-    }
     __syncthreads();
 
-    // Rule elision (workgroup-uniform): the reference's "factor that underflowed to 0 is skipped" tests (Q1) cost 2 packed
+    // wavefront -> its WTX x WTY block of threads.  Everything derived from `wave` is wave-uniform (scalar registers, scalar branches)
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const int tx0 = WTX * (wave % WAVES_X), ty0 = WTY * (wave / WAVES_X);
+    const int tx = tx0 + lane % WTX, ty = ty0 + lane / WTX;
+    if (x0 + tx0 * PX >= a.width || y0 + ty0 >= a.height) return;      // the whole wavefront lies outside the image
+
+    // Rule elision (wave-uniform): the reference's "factor that underflowed to 0 is skipped" tests (Q1) cost 2 packed
     // instructions per unit and pass for the colour rule and 3 per unit for the depth rule.  Neither can trip anywhere
-    // in this tile when the tile's own value ranges stay below the thresholds:
-    //   colour: cd(p, q) <= sum_c (max_c - min_c)^2 over the staged pixels           < cd_skip
-    //   depth:  |d_q - avg_p| <= max - min of the staged valid depths (avg_p is a mean of them), x sd  < t_skip
-    // The full-rule code is kept for the tiles that straddle a colour or depth edge.
+    // in this wavefront's pixels when the value ranges of its REGION -- its pixels plus R on every side: each centre and each
+    // tap the wavefront can touch -- stay below the thresholds:
+    //   colour: cd(p, q) <= sum_c (max_c - min_c)^2 over the region's in-image pixels            < cd_skip
+    //   depth:  |d_q - avg_p| <= max - min of the region's valid depths (avg_p is a mean of them), x sd  < t_skip
+    // Each wavefront reduces the statistics of its own region from LDS and branches on them; no barrier follows, so the
+    // wavefronts of one workgroup may run different bodies.  (Until EXPERIMENTS.md Part I item 13 the decision was one per
+    // workgroup, on statistics the loader gathered: the 74-pixel-wide region of a 64x16 tile holds a vertical edge of the
+    // content far more often than a 42x18 one.)
     bool tile_c = CSKIP, tile_d = true;
-    if (ELIDE) {
-        const int rb = (int)s_stat[3] - (int)s_stat[2], rg = (int)s_stat[5] - (int)s_stat[4], rr = (int)s_stat[7] - (int)s_stat[6];
-        if (s_stat[3] >= s_stat[2]) tile_c = CSKIP && (rb * rb + rg * rg + rr * rr >= a.cd_skip);
-        const float range = __uint_as_float(s_stat[1]) - __uint_as_float(s_stat[0]);       // -inf when no valid depth was staged
-        // avg_p is a float32 quotient of float32 sums: it can leave [dmin, dmax] by the rounding of those sums, at most
-        // about (taps + 8) / 2 ulps of dmax -- an absolute slack that a purely relative margin on the range does not cover
-        // when the depths are large and sigma_d is small (1e4 mm at sigma_d = 1 mm)
-        const float slack = __uint_as_float(s_stat[1]) * (float)(WIN * WIN + 8) * 0x1p-24f;
-        tile_d = !((range * 1.0001f + slack) * a.sd < a.t_skip);
+    if constexpr (ELIDE) {
+        constexpr int RWP = (WTX * PX + 2 * R) / 2, RH = WTY + 2 * R;     // region: RWP aligned pairs x RH rows
+        constexpr int NE = RWP * RH;
+        const int sxw = SH + RA - R + tx0 * PX;                            // its first LDS column (even), first LDS row = ty0
+        const int gx0 = x0 + tx0 * PX - R, gy0 = y0 + ty0 - R;             // the same corner in the image
+        // Positive floats order like their bit patterns.  dmin is taken over bits - 1, so that 0 (= invalid) sorts last.
+        uint32_t dmin = 0xffffffffu, dmax = 0u;
+        // colour: channels as packed 16-bit lanes, (b, r) of every pixel in one register, g of a pair of pixels in another
+        uint32_t brmin = 0x00ff00ffu, brmax = 0u, ggmin = 0x00ff00ffu, ggmax = 0u;
+        auto scan = [&](auto masked_tag) {
+            constexpr bool MASKED = decltype(masked_tag)::value;
+            // element e = lane + 64 k of the region, row-major over its pairs: (row, pair, LDS index) advance by 64 elements per step
+            constexpr int QY = 64 / RWP, QP = 64 % RWP;
+            int ry = lane / RWP, rp = lane - ry * RWP;
+            int li = (ty0 + ry) * P + sxw + 2 * rp;
+#pragma unroll
+            for (int k = 0; k < (NE + 63) / 64; k++) {
+                if (k > 0) {
+                    const bool wrap = rp + QP >= RWP;
+                    rp += wrap ? QP - RWP : QP;
+                    ry += wrap ? QY + 1 : QY;
+                    li += wrap ? (QY + 1) * P + 2 * (QP - RWP) : QY * P + 2 * QP;
+                }
+                if (64 * k + 63 < NE || lane + 64 * k < NE) {
+                    const u2 d = *reinterpret_cast<const u2*>(&s_d[li]);
+                    dmin = min(dmin, min(d.x - 1u, d.y - 1u));
+                    dmax = max(dmax, max(d.x, d.y));
+                    if constexpr (CSKIP) {       // (instances without the colour rule need no colour statistics)
+                        const u2 c = *reinterpret_cast<const u2*>(&s_c[li]);
+                        uint32_t lo0 = c.x, lo1 = c.y, hi0 = c.x, hi1 = c.y;
+                        if constexpr (MASKED) {      // pixels staged from outside the image (zeros) do not count
+                            const bool iny = (unsigned)(gy0 + ry) < (unsigned)a.height;
+                            const bool in0 = iny & ((unsigned)(gx0 + 2 * rp) < (unsigned)a.width);
+                            const bool in1 = iny & ((unsigned)(gx0 + 2 * rp + 1) < (unsigned)a.width);
+                            lo0 = in0 ? lo0 : 0x00ffffffu;
+                            lo1 = in1 ? lo1 : 0x00ffffffu;
+                            hi0 = in0 ? hi0 : 0u;
+                            hi1 = in1 ? hi1 : 0u;
+                        }
+                        brmin = pk_min_u16(pk_min_u16(brmin, lo0 & 0x00ff00ffu), lo1 & 0x00ff00ffu);
+                        brmax = pk_max_u16(pk_max_u16(brmax, hi0 & 0x00ff00ffu), hi1 & 0x00ff00ffu);
+                        // v_perm_b32 gathers the bytes (0, g of the second pixel, 0, g of the first)
+                        ggmin = pk_min_u16(ggmin, __builtin_amdgcn_perm(lo1, lo0, 0x0c050c01u));
+                        ggmax = pk_max_u16(ggmax, __builtin_amdgcn_perm(hi1, hi0, 0x0c050c01u));
+                    }
+                }
+            }
+        };
+        // (depths staged from outside the image are 0 = invalid by themselves: only the colours need the mask)
+        if (!CSKIP || (gx0 >= 0 && gx0 + 2 * RWP <= a.width && gy0 >= 0 && gy0 + RH <= a.height)) scan(std::false_type{});
+        else scan(std::true_type{});
+        const uint32_t w_dmin = wave_reduce(dmin, [](uint32_t p, uint32_t q) { return min(p, q); }) + 1u;   // 0: no valid depth
+        const uint32_t w_dmax = wave_reduce(dmax, [](uint32_t p, uint32_t q) { return max(p, q); });
+        if constexpr (CSKIP) {
+            const uint32_t w_brmin = wave_reduce(brmin, pk_min_u16), w_brmax = wave_reduce(brmax, pk_max_u16);
+            const uint32_t w_ggmin = wave_reduce(ggmin, pk_min_u16), w_ggmax = wave_reduce(ggmax, pk_max_u16);
+            const int bmin = w_brmin & 0xffffu, bmax = w_brmax & 0xffffu, rmin = w_brmin >> 16, rmax = w_brmax >> 16;
+            const int gmin = min(w_ggmin & 0xffffu, w_ggmin >> 16), gmax = max(w_ggmax & 0xffffu, w_ggmax >> 16);
+            const int rb = bmax - bmin, rg = gmax - gmin, rr = rmax - rmin;
+            if (bmax >= bmin) tile_c = rb * rb + rg * rg + rr * rr >= a.cd_skip;
+        }
+        if (w_dmax == 0u) {
+            tile_d = false;                       // no valid depth in the region: every tap has weight 0
+        } else {
+            const float range = __uint_as_float(w_dmax) - __uint_as_float(w_dmin);
+            // avg_p is a float32 quotient of float32 sums: it can leave [dmin, dmax] by the rounding of those sums, at most
+            // about (taps + 8) / 2 ulps of dmax -- an absolute slack that a purely relative margin on the range does not cover
+            // when the depths are large and sigma_d is small (1e4 mm at sigma_d = 1 mm)
+            const float slack = __uint_as_float(w_dmax) * (float)(WIN * WIN + 8) * 0x1p-24f;
+            tile_d = !((range * 1.0001f + slack) * a.sd < a.t_skip);
+        }
     }
     KDE_STAGE(if (a.stage_force) { tile_c = CSKIP; tile_d = true; })
-    KDE_STAGE(if (a.stage_counters && tid == 0) {
-        // the body the dispatch below picks for this tile: bit 0 = colour rule compiled in, bit 1 = depth rule
+    KDE_STAGE(if (a.stage_counters && lane == 0) {
+        // the body the dispatch below picks for this wavefront: bit 0 = colour rule compiled in, bit 1 = depth rule
+        // (one count per wavefront that owns at least one pixel)
         int body;
         if constexpr (!ELIDE) body = (CSKIP ? 1 : 0) + 2;
         else if constexpr (WIN >= 15) body = ((CSKIP && tile_c) || tile_d) ? (CSKIP ? 1 : 0) + 2 : 0;
@@ -490,7 +561,6 @@ void jbf_pk_kernel(const FastArgs a)
         atomicAdd(&a.stage_counters[body], 1u);
     })
 
-    const int tx = tid % BX, ty = tid / BX;
     const int xb = x0 + tx * PX, y = y0 + ty;
     if (xb >= a.width || y >= a.height) return;
     const int sx = SH + RA - R + tx * PX;  // LDS column of this thread's first window column (even)
@@ -694,7 +764,7 @@ void jbf_pk_kernel(const FastArgs a)
     }
 }
 
-template <int WIN, int NP, int BX, int BY, bool CACHE, bool VL, bool ELIDE_ON = true, int CR = (CACHE ? WIN : 0)>
+template <int WIN, int NP, int BX, int BY, bool CACHE, bool VL, bool ELIDE_ON = true, int WTX = BX>
 int launch_pk_variant(const JbfLaunch& l, const FastArgs& fa, bool cskip, hipStream_t s)
 {
     FastArgs a = fa;
@@ -705,9 +775,9 @@ int launch_pk_variant(const JbfLaunch& l, const FastArgs& fa, bool cskip, hipStr
     a.div_tx = make_fastdiv24((uint32_t)a.tiles_x, (uint64_t)a.tiles_x * a.tiles_y);
     if (blocks > 0x7fffffffLL) return fail(KDE_ERR_INVALID, "jbf: batch too large for one launch");
     if (cskip)
-        hipLaunchKernelGGL((jbf_pk_kernel<WIN, NP, BX, BY, CACHE, true, VL, ELIDE_ON, CR>), dim3((unsigned)blocks), dim3(BX * BY), 0, s, a);
+        hipLaunchKernelGGL((jbf_pk_kernel<WIN, NP, BX, BY, CACHE, true, VL, ELIDE_ON, WTX>), dim3((unsigned)blocks), dim3(BX * BY), 0, s, a);
     else
-        hipLaunchKernelGGL((jbf_pk_kernel<WIN, NP, BX, BY, CACHE, false, VL, ELIDE_ON, CR>), dim3((unsigned)blocks), dim3(BX * BY), 0, s, a);
+        hipLaunchKernelGGL((jbf_pk_kernel<WIN, NP, BX, BY, CACHE, false, VL, ELIDE_ON, WTX>), dim3((unsigned)blocks), dim3(BX * BY), 0, s, a);
     KDE_HIP_TRY(hipGetLastError());
     return KDE_OK;
 }
@@ -746,6 +816,12 @@ struct Variant {
     {"w" #WIN "-pk" #NP "-" #BX "x" #BY "-" #CACHE "-v1", WIN, true, &launch_pk_variant<WIN, NP, BX, BY, CACHE, false>}
 #define KN(WIN, NP, BX, BY, CACHE) \
     {"w" #WIN "-pk" #NP "-" #BX "x" #BY "-" #CACHE "-v4-noelide", WIN, true, &launch_pk_variant<WIN, NP, BX, BY, CACHE, true, false>}
+// KQ: wavefronts of 8x8 threads inside the tile (WTX = 8) instead of BX x (64 / BX); KR ("-rows"): the plain mapping of a tile
+// whose built-in kernel is a KQ one
+#define KQ(WIN, NP, BX, BY, CACHE) \
+    {"w" #WIN "-pk" #NP "-" #BX "x" #BY "-" #CACHE "-v4", WIN, true, &launch_pk_variant<WIN, NP, BX, BY, CACHE, true, true, 8>}
+#define KR(WIN, NP, BX, BY, CACHE) \
+    {"w" #WIN "-pk" #NP "-" #BX "x" #BY "-" #CACHE "-v4-rows", WIN, true, &launch_pk_variant<WIN, NP, BX, BY, CACHE, true>}
 const Variant kVariants[] = {
     // the FIRST variant listed for a window is the built-in choice (interleaved A/B sweep on MI355X,
     // profiles/r03_sweep_k1_variants.log); the others stay selectable for the tile sweep of BASELINE config 3.
@@ -756,9 +832,14 @@ const Variant kVariants[] = {
     K(7, 1, 16, 16, true),  K(7, 1, 32, 8, true),   KS(7, 1, 32, 8, true),  K(7, 1, 32, 8, false),  V(7, 1, 64, 4, true),
     // tiles (pixels) of BASELINE config 3's sweep: 64x16 / 32x16 / 64x8 / 128x8 with 4 or 2 pixels per thread (packed pairs),
     // and the scalar kernels at 2 and 1 pixels per thread (32x16, 32x8)
-    K(11, 2, 16, 16, false), KS(11, 2, 16, 16, false), KS(11, 1, 16, 16, false), K(11, 1, 16, 16, false), K(11, 1, 32, 8, false),
+    // window 11 (EXPERIMENTS.md Part I item 13): the 64x16-pixel tile with its wavefronts as 8x8-thread quarters, 32x8 pixels each --
+    // the squarer footprint meets fewer of the content's edges than the 64x4 pixels of a row-major wavefront, so fewer wavefronts
+    // run a rule body.  "-rows" is the same tile with the row-major mapping, w11-pk2-8x32 a 32x32-pixel tile whose row-major
+    // wavefronts have the 32x8 footprint by themselves (measured equal to the built-in choice)
+    KQ(11, 2, 16, 16, false), KR(11, 2, 16, 16, false), K(11, 2, 8, 32, false),
+    KS(11, 2, 16, 16, false), KS(11, 1, 16, 16, false), K(11, 1, 16, 16, false), K(11, 1, 32, 8, false),
     KS(11, 1, 32, 8, false), KS(11, 2, 32, 8, false), V(11, 2, 16, 16, false), V(11, 1, 32, 8, false),
-    KN(11, 2, 16, 16, false),      // the default without tile-level rule elision: the window's data-independent floor
+    KN(11, 2, 16, 16, false),      // the default without rule elision: the window's data-independent floor
     K(19, 1, 16, 16, false), KS(19, 1, 16, 16, false), KS(19, 2, 16, 16, false), K(19, 2, 16, 16, false), K(19, 1, 32, 8, false),
     KS(19, 1, 32, 8, false), KS(19, 2, 32, 8, false), V(19, 2, 16, 16, false), V(19, 1, 32, 8, false),
     KN(19, 1, 16, 16, false),
@@ -767,7 +848,7 @@ const Variant kVariants[] = {
     // (further down) read it from a device table.  Same kernel template, vector loader; the pass-1 arguments stay in registers at window 3 and are recomputed from window 9 on.
     // First listed = built-in choice (tools/sweep_jbf.py, profiles/r04_sweep_k1_windows.log)
     K(3, 1, 16, 16, true),   K(3, 2, 16, 16, true),
-    K(9, 2, 16, 16, false),  K(9, 1, 16, 16, false),
+    K(9, 2, 16, 16, false),  K(9, 1, 16, 16, false),  KN(9, 2, 16, 16, false),
     K(13, 2, 16, 16, false), K(13, 1, 16, 16, false),
     K(15, 1, 16, 16, false), K(15, 2, 16, 16, false),
     K(17, 1, 16, 16, false), K(17, 2, 16, 16, false),
@@ -780,6 +861,8 @@ static_assert(sizeof(FastArgs) <= 4096, "FastArgs is passed by value as the kern
 #undef K
 #undef KS
 #undef KN
+#undef KQ
+#undef KR
 constexpr int kNumVariants = sizeof(kVariants) / sizeof(kVariants[0]);
 
 }  // namespace

@@ -40,7 +40,11 @@ class StageCtl:
         self._l = l
 
     def set(self, jbf_avg=None, ers_avg=None, ers_dev=None, counters=None, force_full_rules=False):
-        """torch CUDA tensors (float32 sinks, int32[8] counters) or None"""
+        """torch CUDA tensors (float32 sinks, int32[8] counters) or None.
+        counters[0..3]: how often each rule-specialised body ran (bit 0 = colour rule, bit 1 = depth rule).  K1's packed
+        kernels count once per WAVEFRONT that owns at least one pixel (lane 0 of the wavefront; a wavefront wholly outside the
+        image does not count) -- they decide per wavefront, so the total depends on the kernel variant's wavefront footprint.
+        counters[4..7] are K10's, once per tile (include/kde_test_hooks.h)."""
         p = lambda t: None if t is None else t.data_ptr()
         rc = self._l.kde_stage_set(p(jbf_avg), p(ers_avg), p(ers_dev), p(counters), 1 if force_full_rules else 0)
         if rc:
