@@ -1,0 +1,7 @@
+# The objects of libkde_hip.so, included by this directory's Makefile and by tools/hooks/Makefile (the stage build of
+# the same sources): a new source file is added here and nowhere else.
+#   API_OBJS     host code, kde_api*.cpp: the extern "C" surface, one file per family of reference classes
+#   KERNEL_OBJS  kernels and their launchers, *.hip
+API_OBJS    := kde_api.o kde_api_jbf.o kde_api_dimconv.o kde_api_dasp_ers.o kde_api_pipeline.o kde_api_normals.o kde_api_nasp.o kde_api_les.o kde_api_proj.o
+KERNEL_OBJS := jbf_kernels.o jbf_fast.o stream_kernels.o dasp_kernels.o ers_kernels.o spdsr_kernels.o normal_kernels.o nasp_kernels.o les_kernels.o proj_kernels.o
+OBJS        := $(API_OBJS) $(KERNEL_OBJS)

@@ -150,3 +150,19 @@ print(json.dumps(out))
     from kinectdepthmapenhancement_amd import _native as N
     bad = {k: v for k, v in res.items() if v != (N.KDE_OK if k.endswith("_destroy") else N.KDE_ERR_INVALID)}
     assert not bad, bad
+
+
+def test_refused_calls_answer_as_they_did_before_the_api_was_split():
+    """tests/golden/abi_refusals.json: the return code and the message of every call the library refuses before it touches
+    HIP (all-zero arguments for every entry point; a valid out-pointer for every create, with all-zero arguments and with a
+    frame but max_batch = 0), recorded by tools/abi_refusals.py from the library as it was while kde_api.cpp held every
+    handle.  The same calls in the same order, in a child process, must give the same codes and the same messages."""
+    import json
+    golden = json.load(open(os.path.join(ROOT, "tests", "golden", "abi_refusals.json")))
+    assert sum(r["mode"] == "zero" for r in golden) == 132 and sum(r["mode"] == "create" for r in golden) == 16
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "abi_refusals.py")], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
+    got = json.loads(r.stdout)
+    assert [(g["mode"], g["name"]) for g in got] == [(g["mode"], g["name"]) for g in golden]
+    assert [g for g, w in zip(got, golden) if g["rc"] != w["rc"]] == []
+    assert [(g, w["message"]) for g, w in zip(got, golden) if g["message"] != w["message"]] == []
