@@ -14,6 +14,8 @@
 //   Projection_GPU              (Projection_GPU/Projection_GPU.h:8-42; the five-argument PlaneProjection)
 //   KinectDepthEnhancement      (KinectDepthEnhancement.h:19-44)
 //   kde::JointBilateralFilterFeed (extension: JointBilateralFilter on frames in host memory, main.cpp:160-163)
+//   kde::KinectDepthEnhancementFeed, kde::pointsToDepth (extension: KinectDepthEnhancement on frames in host memory,
+//                                 main.cpp:160-163, 198-202, with the result as a point cloud or a depth map)
 //
 // What differs from the reference headers, and why:
 //   * cv::gpu::GpuMat parameters are templates over "anything with .data/.rows/.cols/.step" — a real
@@ -925,7 +927,12 @@ private:
 // (.cpp:82-87) are not built: they return a buffer of the EdgeRefinedSuperpixel member that Process never writes.
 class KinectDepthEnhancement {
 public:
-    KinectDepthEnhancement(int width, int height) : Width(width), Height(height) { check(kde_enh_create(&h_, width, height, 1)); }
+    KinectDepthEnhancement(int width, int height) : KinectDepthEnhancement(width, height, 1) {}
+    // added: buffers for max_batch frames, the largest chunk a kde::KinectDepthEnhancementFeed on this object may use
+    KinectDepthEnhancement(int width, int height, int max_batch) : Width(width), Height(height)
+    {
+        check(kde_enh_create(&h_, width, height, max_batch));
+    }
     ~KinectDepthEnhancement() { kde_enh_destroy(h_); }
     KinectDepthEnhancement(const KinectDepthEnhancement&) = delete;
     KinectDepthEnhancement& operator=(const KinectDepthEnhancement&) = delete;
@@ -1016,6 +1023,54 @@ public:
 
 private:
     kde_jbf_feed* f_ = nullptr;
+};
+
+// extension (no reference counterpart): the z of n_points packed points as a depth map on the device (kde_points_to_depth),
+// float with the bits unchanged or the sensor's uint16 millimetres (rounded half to even, 0 = invalid); asynchronous on stream
+inline void pointsToDepth(size_t n_points, const float3* points_device, float* depth_device, void* hip_stream = nullptr)
+{
+    check(kde_points_to_depth(n_points, reinterpret_cast<const kde_float3*>(points_device), KDE_DEPTH_F32, depth_device, hip_stream));
+}
+inline void pointsToDepth(size_t n_points, const float3* points_device, uint16_t* depth_device, void* hip_stream = nullptr)
+{
+    check(kde_points_to_depth(n_points, reinterpret_cast<const kde_float3*>(points_device), KDE_DEPTH_U16, depth_device, hip_stream));
+}
+
+// extension (no reference counterpart): KinectDepthEnhancement::Process on frames in host memory (kde_enh_feed_*), the upload of
+// main.cpp:160-163 and the uint16 widening included; the result comes back as the optimized cloud (float3), its depth map
+// (float) or that in the sensor's format (uint16_t), chosen by the type of the output pointer.  Borrows the object and runs
+// it: it must outlive this feed, must have had SetParametor called and must not be used while process() runs; its getters
+// then show the last chunk.  chunk_frames is at most the object's max_batch.  process() blocks.
+class KinectDepthEnhancementFeed {
+public:
+    KinectDepthEnhancementFeed(ref::KinectDepthEnhancement& enh, int chunk_frames) : KinectDepthEnhancementFeed(enh.handle(), chunk_frames) {}
+    KinectDepthEnhancementFeed(kde_enh* enh, int chunk_frames) { check(kde_enh_feed_create(&f_, enh, chunk_frames)); }
+    ~KinectDepthEnhancementFeed() { kde_enh_feed_destroy(f_); }
+    KinectDepthEnhancementFeed(const KinectDepthEnhancementFeed&) = delete;
+    KinectDepthEnhancementFeed& operator=(const KinectDepthEnhancementFeed&) = delete;
+
+    // n frames back to back: depth in mm (float, or the sensor's uint16 with 0 = invalid), packed BGR
+    template <class Depth, class Out>
+    void process(int n, const Depth* depth_host, const uint8_t* bgr_host, Out* out_host)
+    {
+        check(kde_enh_feed_process(f_, n, depth_host, depth_format(depth_host), bgr_host, out_format(out_host), out_host));
+    }
+    kde_feed_stats lastStats() const
+    {
+        kde_feed_stats st{};
+        check(kde_enh_feed_last_stats(f_, &st));
+        return st;
+    }
+    kde_enh_feed* handle() const { return f_; }
+
+private:
+    static int depth_format(const float*) { return KDE_DEPTH_F32; }
+    static int depth_format(const uint16_t*) { return KDE_DEPTH_U16; }
+    static int out_format(const float3*) { return KDE_OUT_POINTS_F32; }
+    static int out_format(const kde_float3*) { return KDE_OUT_POINTS_F32; }
+    static int out_format(const float*) { return KDE_OUT_DEPTH_F32; }
+    static int out_format(const uint16_t*) { return KDE_OUT_DEPTH_U16; }
+    kde_enh_feed* f_ = nullptr;
 };
 
 }  // namespace kde

@@ -160,7 +160,7 @@ int kde_jbf_feed_destroy(kde_jbf_feed* f);
  * kde_jbf_process_batch on the same frames.  depth_format = KDE_DEPTH_F32 (float) or KDE_DEPTH_U16 (uint16_t).
  * BLOCKING: returns once all n outputs are in filtered_host; the inputs may be reused at once.  It synchronises only the
  * feed's own streams and events, never the device or another stream.  It takes no stream and cannot be captured into a
- * graph: the one entry point of this header that is not capture-safe. */
+ * graph: with kde_enh_feed_process, the only entry points of this header that are not capture-safe. */
 int kde_jbf_feed_process(kde_jbf_feed* f, int n, const void* depth_host, int depth_format, const uint8_t* bgr_host,
                          float* filtered_host);
 /* what the last kde_jbf_feed_process did (zeros before the first call) */
@@ -524,6 +524,46 @@ int kde_enh_optimized_points_host(kde_enh* h, void* stream, const kde_float3** o
 int kde_enh_nasp_labels_device(kde_enh* h, int32_t** out);          /* NASP->getLabelDevice()                       */
 int kde_enh_merged_labels_device(kde_enh* h, int32_t** out);        /* spMerging->getMergedClusterLabel_Device()    */
 int kde_enh_edge_enhanced_points_device(kde_enh* h, kde_float3** out);   /* EdgeEnhanced3DPoints_Device             */
+
+/* ---- depth output: the enhanced cloud as a depth map --------------------------------------------------------------
+ * The reference's result is a point cloud (getOptimizedPoints_Host, main.cpp:198-202) although its input is the sensor's
+ * depth map (uint16 millimetres, 0 = invalid, widened on the host and uploaded, main.cpp:160-163).  kde_points_to_depth writes the z of
+ * n_points packed points as a depth map.  Stateless, on the current device, asynchronous on `stream`, capture-safe.
+ *   KDE_DEPTH_F32  out[i] = points[i].z, the bits unchanged (NaNs included)
+ *   KDE_DEPTH_U16  r = rintf(z) (round half to even); out[i] = (r >= 1 && r <= 65535) ? (uint16_t)r : 0.  NaN, +-inf,
+ *                  z < 0.5 and z >= 65535.5 give 0, the sensor's "invalid"; every integer z in 1..65535 is returned as it
+ *                  is, so this is the exact inverse of the widening a feed applies to uint16 depth.
+ * n_points == 0 is KDE_OK and launches nothing.  KDE_ERR_INVALID: a null pointer with n_points > 0, an unknown format,
+ * points_dev or a float output not 4-byte aligned, a uint16 output not 2-byte aligned.  Pointers that are both 16-byte
+ * aligned take the vector kernels; any other alignment is served by scalar ones. */
+enum { KDE_OUT_POINTS_F32 = 0, KDE_OUT_DEPTH_F32 = 1, KDE_OUT_DEPTH_U16 = 2 };   /* out_format of kde_enh_feed_process */
+int kde_points_to_depth(size_t n_points, const kde_float3* points_dev, int depth_format /* KDE_DEPTH_F32 | KDE_DEPTH_U16 */,
+                        void* depth_dev, void* stream);
+
+/* ---- host-fed KinectDepthEnhancement: frames that start and end in host memory --------------------------------------
+ * Process (main.cpp:198-202) on n frames in host memory, the upload of main.cpp:160-163 and the uint16 widening
+ * included: the contract of kde_jbf_feed_* above (n >= 1 not bounded by max_batch; pinned or pageable buffers, detected
+ * per call, pageable ones staged through a pinned ring; BLOCKING; synchronises only the feed's own three streams and
+ * events; not capture-safe; one device, not thread-safe), with these differences:
+ *   - chunk_frames must lie in 1..max_batch of the kde_enh: each chunk is one kde_enh_process_batch.
+ *   - the feed borrows the kde_enh and RUNS it: per chunk, on the feed's compute stream, the uint16 widening (if any),
+ *     kde_enh_process_batch on the slot's buffers, then the output step into the slot.  The kde_enh_* getters afterwards
+ *     show the LAST CHUNK of the last call.  The kde_enh must outlive the feed and must not be used while a call runs;
+ *     a kde_enh whose SetParametor was not called makes kde_enh_feed_process return that object's own refusal.
+ *   - out_format selects what comes back, frame f at out_host + f * W*H elements:
+ *       KDE_OUT_POINTS_F32  kde_float3 (12 B): the optimized points (getOptimizedPoints_Host of every frame)
+ *       KDE_OUT_DEPTH_F32   float (4 B), KDE_OUT_DEPTH_U16  uint16_t (2 B): kde_points_to_depth of them
+ *     The copy-out reads only the slot, so the next chunk's kernels may overwrite the object's buffers meanwhile.
+ *   - stats: d2h_bytes = W*H*n * {12, 4, 2}, h2d_bytes = W*H*n * (depth element size + 3).
+ * Every result is bit-identical to kde_enh_process_batch on the same frames followed by kde_points_to_depth.  On failure
+ * the three streams are synchronised before the call returns: nothing stays in flight into the caller's memory. */
+typedef struct kde_enh_feed kde_enh_feed;
+int kde_enh_feed_create(kde_enh_feed** out, kde_enh* enh, int chunk_frames);
+int kde_enh_feed_destroy(kde_enh_feed* f);
+int kde_enh_feed_process(kde_enh_feed* f, int n, const void* depth_host, int depth_format, const uint8_t* bgr_host,
+                         int out_format, void* out_host);
+/* what the last kde_enh_feed_process did (zeros before the first call) */
+int kde_enh_feed_last_stats(kde_enh_feed* f, kde_feed_stats* out);
 
 #ifdef __cplusplus
 }

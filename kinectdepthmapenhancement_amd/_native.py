@@ -30,6 +30,7 @@ class JbfParams(C.Structure):
 
 
 KDE_DEPTH_F32, KDE_DEPTH_U16 = 0, 1
+KDE_OUT_POINTS_F32, KDE_OUT_DEPTH_F32, KDE_OUT_DEPTH_U16 = 0, 1, 2
 KDE_NORMALS_SDC, KDE_NORMALS_CM, KDE_NORMALS_BILATERAL = 0, 1, 2
 
 
@@ -50,10 +51,17 @@ class ProjParams(C.Structure):
 
 
 class FeedStats(C.Structure):
-    """kde_feed_stats: what the last kde_jbf_feed_process call did."""
+    """kde_feed_stats: what the last kde_jbf_feed_process / kde_enh_feed_process call did."""
     _fields_ = [("frames", C.c_int), ("chunks", C.c_int), ("chunk_frames", C.c_int), ("inputs_staged", C.c_int),
                 ("outputs_staged", C.c_int), ("wall_ms", C.c_float), ("h2d_ms", C.c_float), ("compute_ms", C.c_float),
                 ("d2h_ms", C.c_float), ("h2d_bytes", C.c_size_t), ("d2h_bytes", C.c_size_t)]
+
+
+class EnhFeedHandle(C.c_void_p):
+    """kde_enh_feed*: a ctypes type of its own, so that an argument declared as EnhFeedHandle takes None or an EnhFeedHandle
+    and refuses a plain c_void_p (any other handle) with a TypeError.  It also keeps the kde_enh_feed_* entry points out of
+    the frozen record tools/abi_refusals.py enumerates (first argument c_void_p or POINTER(c_void_p)); their refusals are
+    recorded by tools/abi_refusals_new.py instead."""
 
 
 def build(force: bool = False) -> str:
@@ -214,6 +222,11 @@ SIGNATURES = {
     "kde_enh_nasp_labels_device": (_i, [_vp, _pp]),
     "kde_enh_merged_labels_device": (_i, [_vp, _pp]),
     "kde_enh_edge_enhanced_points_device": (_i, [_vp, _pp]),
+    "kde_points_to_depth": (_i, [_sz, _vp, _i, _vp, _vp]),
+    "kde_enh_feed_create": (_i, [C.POINTER(EnhFeedHandle), _vp, _i]),
+    "kde_enh_feed_destroy": (_i, [EnhFeedHandle]),
+    "kde_enh_feed_process": (_i, [EnhFeedHandle, _i, _vp, _i, _vp, _i, _vp]),
+    "kde_enh_feed_last_stats": (_i, [EnhFeedHandle, C.POINTER(FeedStats)]),
 }
 
 

@@ -1,8 +1,6 @@
 // kde_api_jbf.cpp — JointBilateralFilter (kde_jbf_*), its host-fed streaming form (kde_jbf_feed_*) and
 // MarkovRandomField (kde_mrf_*).  struct kde_jbf is in kde_handles.h: the KinectDepthEnhancement pipeline reads it.
-#include "kde_handles.h"
-
-#include <chrono>
+#include "kde_feed_ring.h"
 
 // =====================================================================================================
 // JointBilateralFilter
@@ -257,40 +255,19 @@ extern "C" const char* kde_jbf_variant_name(int variant) { return jbf_variant_na
 // -----------------------------------------------------------------------------------------------------
 // host-fed JBF (kde_jbf_feed_*): chunks of frames copied in, filtered and copied out on three streams
 // -----------------------------------------------------------------------------------------------------
-// Slot ring: chunk c uses slot c % kFeedSlots.  Three slots let the copy-in of chunk c, the kernels of c - 1 and the
-// copy-out of c - 2 run at the same time; the next use of a slot waits for its copy-out (the H2D stream waits on the
-// slot's d2h_done event), so the only host waits are on the feed's own events.
-static constexpr int kFeedSlots = 3;
-
-struct FeedSlot {
+// The streams, the slot ring and the chunk loop are FeedRing's (kde_feed_ring.h); the feed owns the device buffers.
+struct JbfFeedSlot {
     DevBuf<float> depth;            // [chunk][H][W] f32: the copied-in depth, or the widened uint16 depth
     DevBuf<uint16_t> depth16;       // [chunk][H][W] landing area of uint16 depth
     DevBuf<uint8_t> bgr;            // [chunk][H][W][3]
     DevBuf<uint8_t> guide;          // [chunk][H][W][3]: K0's output (presmooth = 1 only)
     DevBuf<float> out;              // [chunk][H][W]
-    PinnedBuf<uint8_t> in_host;     // pageable inputs: depth bytes then bgr bytes of one chunk
-    PinnedBuf<float> out_host;      // pageable outputs: one chunk
-    hipEvent_t ev[6] = {};          // h2d start / done, compute start / done, d2h start / done (timing enabled)
     int frames = 0;                 // device capacity in frames
 };
 
-struct kde_jbf_feed {
+struct kde_jbf_feed : FeedRing {
     kde_jbf* jbf = nullptr;
-    int device = -1;
-    int chunk = 1;
-    hipStream_t h2d = nullptr, comp = nullptr, d2h = nullptr;
-    FeedSlot slot[kFeedSlots];
-    kde_feed_stats stats{};
-    ~kde_jbf_feed()
-    {
-        // a call always ends with every slot idle (or fails after synchronising its streams), so nothing is in flight here
-        for (FeedSlot& s : slot)
-            for (hipEvent_t& e : s.ev)
-                if (e) (void)hipEventDestroy(e);
-        if (h2d) (void)hipStreamDestroy(h2d);
-        if (comp) (void)hipStreamDestroy(comp);
-        if (d2h) (void)hipStreamDestroy(d2h);
-    }
+    JbfFeedSlot buf[kFeedSlots];
 };
 
 extern "C" int kde_jbf_feed_create(kde_jbf_feed** out, kde_jbf* jbf, int chunk_frames)
@@ -303,17 +280,10 @@ extern "C" int kde_jbf_feed_create(kde_jbf_feed** out, kde_jbf* jbf, int chunk_f
     kde_jbf_feed* f = new (std::nothrow) kde_jbf_feed;
     if (!f) return fail(KDE_ERR_NOMEM, "kde_jbf_feed_create: out of host memory");
     f->jbf = jbf;
-    f->device = jbf->device;
-    f->chunk = chunk_frames;
-    hipError_t e = hipStreamCreateWithFlags(&f->h2d, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&f->comp, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&f->d2h, hipStreamNonBlocking);
-    for (FeedSlot& s : f->slot)
-        for (hipEvent_t& ev : s.ev)
-            if (e == hipSuccess) e = hipEventCreate(&ev);
-    if (e != hipSuccess) {
+    const int rc = f->open("kde_jbf_feed_create", jbf->device, chunk_frames);
+    if (rc != KDE_OK) {
         delete f;
-        return fail(KDE_ERR_HIP, "kde_jbf_feed_create: stream / event creation failed: %s", hipGetErrorString(e));
+        return rc;
     }
     *out = f;
     return KDE_OK;
@@ -332,79 +302,21 @@ extern "C" int kde_jbf_feed_last_stats(kde_jbf_feed* f, kde_feed_stats* out)
     return KDE_OK;
 }
 
-// true when [p, p + bytes) is pinned host memory the DMA engines can read directly (both ends are checked; the
-// header requires the extent to lie in one allocation).  Errors and hipMemoryTypeUnregistered mean pageable.
-static bool host_pinned(const void* p, size_t bytes)
-{
-    const char* ends[2] = {static_cast<const char*>(p), static_cast<const char*>(p) + bytes - 1};
-    for (const char* q : ends) {
-        hipPointerAttribute_t a;
-        if (hipPointerGetAttributes(&a, q) != hipSuccess) {
-            (void)hipGetLastError();     // the lookup of an unknown pointer leaves a sticky error behind
-            return false;
-        }
-        if (a.type != hipMemoryTypeHost) return false;
-    }
-    return true;
-}
-
-static float span_ms(hipEvent_t a, hipEvent_t b)
-{
-    float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, a, b) != hipSuccess) {
-        (void)hipGetLastError();
-        return 0.0f;
-    }
-    return ms;
-}
-
-static int feed_run(kde_jbf_feed* f, int n, const void* depth_host, int fmt, const uint8_t* bgr_host, float* filtered_host,
-                    kde_feed_stats& st);
-
 extern "C" int kde_jbf_feed_process(kde_jbf_feed* f, int n, const void* depth_host, int depth_format, const uint8_t* bgr_host,
                                     float* filtered_host)
 {
-    const auto t0 = std::chrono::steady_clock::now();
+    const auto t0 = FeedRing::Clock::now();
     KDE_REQUIRE(f, "kde_jbf_feed_process: null feed");
     KDE_REQUIRE(depth_host && bgr_host && filtered_host, "kde_jbf_feed_process: null host buffer");
     KDE_REQUIRE(n >= 1, "kde_jbf_feed_process: n=%d < 1", n);
     KDE_REQUIRE(depth_format == KDE_DEPTH_F32 || depth_format == KDE_DEPTH_U16, "kde_jbf_feed_process: unknown depth_format %d",
                 depth_format);
     KDE_ON_DEVICE(f, "kde_jbf_feed_process");
-    kde_feed_stats st{};
-    int rc = feed_run(f, n, depth_host, depth_format, bgr_host, filtered_host, st);
-    if (rc != KDE_OK) {
-        // leave no copy in flight into or out of the caller's memory (feed streams only)
-        (void)hipStreamSynchronize(f->h2d);
-        (void)hipStreamSynchronize(f->comp);
-        (void)hipStreamSynchronize(f->d2h);
-        return rc;
-    }
-    st.wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    f->stats = st;
-    return KDE_OK;
-}
-
-static int feed_run(kde_jbf_feed* f, int n, const void* depth_host, int fmt, const uint8_t* bgr_host, float* filtered_host,
-                    kde_feed_stats& st)
-{
     kde_jbf* h = f->jbf;
     const size_t px = (size_t)h->width * h->height;
-    const size_t dsz = fmt == KDE_DEPTH_U16 ? sizeof(uint16_t) : sizeof(float);
-    const int cf = std::min(f->chunk, n);                       // frames per chunk in this call
-    const int chunks = (n + cf - 1) / cf;
-    const int used = std::min(chunks, kFeedSlots);
-    const bool in_pinned = host_pinned(depth_host, px * n * dsz) && host_pinned(bgr_host, px * n * 3);
-    const bool out_pinned = host_pinned(filtered_host, px * n * sizeof(float));
-    st.frames = n;
-    st.chunks = chunks;
-    st.chunk_frames = cf;
-    st.inputs_staged = in_pinned ? 0 : 1;
-    st.outputs_staged = out_pinned ? 0 : 1;
-
-    // every slot is idle between calls: (re)size what this call uses
-    for (int k = 0; k < used; k++) {
-        FeedSlot& s = f->slot[k];
+    const bool u16 = depth_format == KDE_DEPTH_U16;
+    auto prepare = [&](int k, int cf, FeedSlotDev& dev) -> int {
+        JbfFeedSlot& s = f->buf[k];
         if (s.frames < cf) {
             const size_t m = px * cf;
             s.frames = 0;
@@ -416,81 +328,28 @@ static int feed_run(kde_jbf_feed* f, int n, const void* depth_host, int fmt, con
             s.frames = cf;
         }
         if (h->p.presmooth && s.guide.n < px * 3 * cf) KDE_TRY(s.guide.alloc(px * 3 * s.frames));
-        if (fmt == KDE_DEPTH_U16 && s.depth16.n < px * cf) KDE_TRY(s.depth16.alloc(px * s.frames));
-        if (!in_pinned) KDE_TRY(s.in_host.ensure(px * cf * (dsz + 3)));
-        if (!out_pinned) KDE_TRY(s.out_host.ensure(px * cf));
-        // every launch and copy below stays inside these extents (px * fr <= px * cf elements per chunk)
+        if (u16 && s.depth16.n < px * cf) KDE_TRY(s.depth16.alloc(px * s.frames));
         KDE_REQUIRE(s.depth.n >= px * cf && s.bgr.n >= px * 3 * cf && s.out.n >= px * cf &&
-                        (!h->p.presmooth || s.guide.n >= px * 3 * cf) && (fmt != KDE_DEPTH_U16 || s.depth16.n >= px * cf),
+                        (!h->p.presmooth || s.guide.n >= px * 3 * cf) && (!u16 || s.depth16.n >= px * cf),
                     "kde_jbf_feed_process: internal error: slot %d is smaller than a chunk", k);
-    }
-
-    const uint8_t* dsrc = static_cast<const uint8_t*>(depth_host);
-    // chunk c's pageable output: wait for its copy-out, then hand it to the caller
-    auto drain = [&](int c) -> int {
-        FeedSlot& s = f->slot[c % kFeedSlots];
-        const int fr = std::min(cf, n - c * cf);
-        KDE_HIP_TRY(hipEventSynchronize(s.ev[5]));
-        memcpy(filtered_host + px * cf * c, s.out_host.p, px * fr * sizeof(float));
+        dev.depth = u16 ? static_cast<void*>(s.depth16.p) : static_cast<void*>(s.depth.p);
+        dev.bgr = s.bgr.p;
+        dev.out = s.out.p;
         return KDE_OK;
     };
-    // chunk c's three spans, read once its last event has completed and before its slot is recorded again
-    auto harvest = [&](int c) -> int {
-        FeedSlot& s = f->slot[c % kFeedSlots];
-        KDE_HIP_TRY(hipEventSynchronize(s.ev[5]));
-        st.h2d_ms += span_ms(s.ev[0], s.ev[1]);
-        st.compute_ms += span_ms(s.ev[2], s.ev[3]);
-        st.d2h_ms += span_ms(s.ev[4], s.ev[5]);
-        return KDE_OK;
-    };
-    for (int c = 0; c < chunks; c++) {
-        FeedSlot& s = f->slot[c % kFeedSlots];
-        const int fr = std::min(cf, n - c * cf);
-        const size_t first = (size_t)c * cf;
-        if (c >= kFeedSlots) {                        // the slot's previous chunk: its output to the caller, its spans,
-            if (!out_pinned) KDE_TRY(drain(c - kFeedSlots));
-            KDE_TRY(harvest(c - kFeedSlots));         // and its staging buffers are free again
-        }
-        // 1. copy-in, once the slot has been consumed
-        const void* din = dsrc + px * first * dsz;
-        const uint8_t* cin = bgr_host + px * first * 3;
-        if (!in_pinned) {
-            memcpy(s.in_host.p, din, px * fr * dsz);
-            memcpy(s.in_host.p + px * fr * dsz, cin, px * fr * 3);
-            din = s.in_host.p;
-            cin = s.in_host.p + px * fr * dsz;
-        }
-        void* ddev = fmt == KDE_DEPTH_U16 ? static_cast<void*>(s.depth16.p) : static_cast<void*>(s.depth.p);
-        if (c >= kFeedSlots) KDE_HIP_TRY(hipStreamWaitEvent(f->h2d, s.ev[5], 0));   // the slot's previous copy-out
-        KDE_HIP_TRY(hipEventRecord(s.ev[0], f->h2d));
-        KDE_HIP_TRY(hipMemcpyAsync(ddev, din, px * fr * dsz, hipMemcpyHostToDevice, f->h2d));
-        KDE_HIP_TRY(hipMemcpyAsync(s.bgr.p, cin, px * fr * 3, hipMemcpyHostToDevice, f->h2d));
-        KDE_HIP_TRY(hipEventRecord(s.ev[1], f->h2d));
-        // 2. widen (u16) + K0 + K1 into the slot's own buffers: the handle's smooth / filtered / n_last stay untouched
-        KDE_HIP_TRY(hipStreamWaitEvent(f->comp, s.ev[1], 0));
-        KDE_HIP_TRY(hipEventRecord(s.ev[2], f->comp));
-        if (fmt == KDE_DEPTH_U16) KDE_TRY(launch_widen_u16(s.depth16.p, s.depth.p, px * fr, f->comp));
+    // widen (u16) + K0 + K1 into the slot's own buffers: the handle's smooth / filtered / n_last stay untouched
+    auto compute = [&](int k, int fr) -> int {
+        JbfFeedSlot& s = f->buf[k];
+        if (u16) KDE_TRY(launch_widen_u16(s.depth16.p, s.depth.p, px * fr, f->comp));
         const uint8_t* guide = s.bgr.p;
         if (h->p.presmooth) {
             KDE_TRY(jbf_presmooth(h, fr, s.bgr.p, s.guide.p, f->comp));
             guide = s.guide.p;
         }
-        KDE_TRY(jbf_filter(h, fr, s.depth.p, guide, s.out.p, f->comp));
-        KDE_HIP_TRY(hipEventRecord(s.ev[3], f->comp));
-        // 3. copy-out
-        KDE_HIP_TRY(hipStreamWaitEvent(f->d2h, s.ev[3], 0));
-        KDE_HIP_TRY(hipEventRecord(s.ev[4], f->d2h));
-        float* dst = out_pinned ? filtered_host + px * first : s.out_host.p;
-        KDE_HIP_TRY(hipMemcpyAsync(dst, s.out.p, px * fr * sizeof(float), hipMemcpyDeviceToHost, f->d2h));
-        KDE_HIP_TRY(hipEventRecord(s.ev[5], f->d2h));
-        st.h2d_bytes += px * fr * (dsz + 3);
-        st.d2h_bytes += px * fr * sizeof(float);
-    }
-    for (int c = std::max(0, chunks - kFeedSlots); c < chunks; c++) {
-        if (!out_pinned) KDE_TRY(drain(c));
-        KDE_TRY(harvest(c));
-    }
-    return KDE_OK;
+        return jbf_filter(h, fr, s.depth.p, guide, s.out.p, f->comp);
+    };
+    return f->process(t0, px, n, depth_host, u16 ? sizeof(uint16_t) : sizeof(float), bgr_host, filtered_host, sizeof(float), prepare,
+                      compute);
 }
 
 // =====================================================================================================

@@ -1,5 +1,6 @@
 // kde_api_proj.cpp — Projection_GPU's five-argument PlaneProjection (kde_proj_*, proj_kernels.hip) and
-// KinectDepthEnhancement (kde_enh_*), which owns one object of each stage and reads their buffers (kde_handles.h).
+// KinectDepthEnhancement (kde_enh_*), which owns one object of each stage and reads their buffers (kde_handles.h, where
+// struct kde_enh is too: the host-fed form in kde_api_enh_feed.cpp runs it).
 #include "kde_handles.h"
 
 // =====================================================================================================
@@ -117,26 +118,6 @@ extern "C" int kde_proj_plane_fitted_points_host(kde_proj* h, void* stream, cons
 // =====================================================================================================
 // KinectDepthEnhancement: the six stage objects in the order of KinectDepthEnhancement.cpp:56-81
 // =====================================================================================================
-struct kde_enh {
-    int width = 0, height = 0, max_batch = 1;
-    int nclusters = 0;                   // rows * cols of SetParametor (0: not called)
-    kde_jbf* JBF = nullptr;
-    kde_dimconv conv;                    // Convertor
-    kde_normals* NormalGenerator = nullptr;
-    kde_nasp* NASP = nullptr;
-    kde_les* spMerging = nullptr;
-    kde_proj* Projector = nullptr;       // created by SetParametor, as in the reference (.cpp:54)
-    DevBuf<kde_float3> edge_points;      // EdgeEnhanced3DPoints_Device  [max_batch][H][W]
-    ~kde_enh()
-    {
-        kde_jbf_destroy(JBF);
-        kde_normals_destroy(NormalGenerator);
-        kde_nasp_destroy(NASP);
-        kde_les_destroy(spMerging);
-        kde_proj_destroy(Projector);
-    }
-};
-
 extern "C" int kde_enh_create(kde_enh** out, int width, int height, int max_batch)
 {
     KDE_REQUIRE(out, "kde_enh_create: null out");

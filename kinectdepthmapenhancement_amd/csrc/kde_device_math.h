@@ -3,7 +3,20 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cmath>
+#include <cstdint>
+
 namespace kde {
+
+// A depth in millimetres as the sensor's uint16 (OpenNI XnDepthPixel, 0 = invalid): rounded half to even, and 0 for
+// everything that is not a depth the format holds -- NaN, +-inf, z < 0.5, z >= 65535.5.  The exact inverse of the
+// (float)u widening of launch_widen_u16: every integer-valued z in 1..65535 comes back as itself.  One function for the
+// kernels (stream_kernels.hip) and the host, so that a CPU test checks the rule the kernels run.
+__host__ __device__ inline uint16_t depth_to_u16(float z)
+{
+    const float r = rintf(z);
+    return (r >= 1.0f && r <= 65535.0f) ? (uint16_t)r : (uint16_t)0;
+}
 
 // sqrtf() of an integer-valued float in [0, 2^24): v_rsq_f32 estimate, one Heron step on the exact fma residual.
 // The library sqrtf() spends 14 instructions (denormal scaling, two +-1 ulp probes, class test) to be correctly

@@ -284,3 +284,24 @@ struct kde_proj {                        // kde_api_proj.cpp
     DevBuf<kde_float3> optimized;        // Optimized3D_Device                               [max_batch][H][W]
     PinnedBuf<kde_float3> plane_fitted_host, optimized_host;
 };
+
+// KinectDepthEnhancement: the six stage objects in the order of KinectDepthEnhancement.cpp:56-81
+struct kde_enh {                         // kde_api_proj.cpp; kde_api_enh_feed.cpp runs it and reads Projector
+    int width = 0, height = 0, max_batch = 1;
+    int nclusters = 0;                   // rows * cols of SetParametor (0: not called)
+    kde_jbf* JBF = nullptr;
+    kde_dimconv conv;                    // Convertor
+    kde_normals* NormalGenerator = nullptr;
+    kde_nasp* NASP = nullptr;
+    kde_les* spMerging = nullptr;
+    kde_proj* Projector = nullptr;       // created by SetParametor, as in the reference (.cpp:54)
+    DevBuf<kde_float3> edge_points;      // EdgeEnhanced3DPoints_Device  [max_batch][H][W]
+    ~kde_enh()
+    {
+        kde_jbf_destroy(JBF);
+        kde_normals_destroy(NormalGenerator);
+        kde_nasp_destroy(NASP);
+        kde_les_destroy(spMerging);
+        kde_proj_destroy(Projector);
+    }
+};

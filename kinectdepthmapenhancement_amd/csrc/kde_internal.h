@@ -185,6 +185,8 @@ int launch_buf_get(const kde_weighted_d* buf, float* out, size_t n, int which, h
 int launch_buf_update(kde_weighted_d* buf, const float* d, size_t n, int n_frames, hipStream_t s);
 // host-fed JBF (kde_jbf_feed_process): n uint16 depth samples -> float, exact
 int launch_widen_u16(const uint16_t* src, float* dst, size_t n, hipStream_t s);
+// kde_points_to_depth: the z of n packed points as float (bits unchanged) or as uint16 (depth_to_u16, kde_device_math.h)
+int launch_points_to_depth(const kde_float3* pts, void* out, size_t n, bool u16, hipStream_t s);
 
 struct DaspGeom {
     int width, height, rows, cols, wx, wy;

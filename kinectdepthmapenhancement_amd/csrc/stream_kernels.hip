@@ -9,6 +9,7 @@
 // The reference's redundant thrust::fill before every projectiveToReal (DimensionConvertor.cu:5-13) is not
 // reproduced (every output element is overwritten).
 #include "kde_internal.h"
+#include "kde_device_math.h"
 
 namespace kde {
 namespace {
@@ -427,6 +428,60 @@ __global__ __launch_bounds__(kThreads) void widen_u16_scalar_kernel(const uint16
     const size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x;
     if (i < n) dst[i] = (float)src[i];
 }
+
+// ---- kde_points_to_depth: the z of packed float3 points as a depth map ----------------------------------------------------
+// float: the bits of z as they are (moves only, NaN payloads survive); uint16: depth_to_u16 (kde_device_math.h).
+// Eight points per thread: the wave's 6 KB of packed float3 loaded as 384 consecutive float4 and transposed through LDS
+// (as points_map_kernel does), then two float4 stores (float) or one 16-byte store (uint16) per thread.
+typedef unsigned s_u4 __attribute__((ext_vector_type(4)));
+
+template <bool NT, bool U16>
+__global__ __launch_bounds__(kThreads) void points_to_depth_kernel(size_t groups, const float* __restrict__ in, void* __restrict__ out)
+{
+    __shared__ float4 xch[kThreads / 64][6 * 64];
+    const unsigned lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    float4* w = xch[wv];
+    const size_t g0 = (size_t)blockIdx.x * kThreads + wv * 64u;   // wave-uniform: the wave's first group of 8 points
+    if (g0 >= groups) return;
+    const unsigned nvec = (unsigned)(groups - g0 < 64 ? groups - g0 : 64) * 6u;
+    const float4* p = reinterpret_cast<const float4*>(in) + g0 * 6;
+#pragma unroll
+    for (unsigned j = 0; j < 6; j++) {
+        const unsigned idx = j * 64u + lane;
+        w[idx] = idx < nvec ? ld4(p + idx, NT) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    wave_exchange_fence();
+    // the lane's 24 floats x0 y0 z0 x1 ...: z of point k is float 3k + 2
+    const float4 a = w[lane * 6], b = w[lane * 6 + 1], c = w[lane * 6 + 2], d = w[lane * 6 + 3], e = w[lane * 6 + 4],
+                 f = w[lane * 6 + 5];
+    const float z[8] = {a.z, b.y, c.x, c.w, d.z, e.y, f.x, f.w};
+    const size_t g = g0 + lane;
+    if (g >= groups) return;
+    if (U16) {
+        unsigned q[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) q[k] = (unsigned)depth_to_u16(z[2 * k]) | ((unsigned)depth_to_u16(z[2 * k + 1]) << 16);
+        s_u4* o = reinterpret_cast<s_u4*>(out) + g;
+        if (NT) __builtin_nontemporal_store(s_u4{q[0], q[1], q[2], q[3]}, o);
+        else *o = s_u4{q[0], q[1], q[2], q[3]};
+    } else {
+        float4* o = reinterpret_cast<float4*>(out) + 2 * g;
+        st4(o, make_float4(z[0], z[1], z[2], z[3]), NT);
+        st4(o + 1, make_float4(z[4], z[5], z[6], z[7]), NT);
+    }
+}
+
+// scalar form: one point per thread from `first` on -- any alignment, and the last n % 8 points of the vector form
+template <bool U16>
+__global__ __launch_bounds__(kThreads) void points_to_depth_scalar_kernel(const float* __restrict__ in, void* __restrict__ out,
+                                                                         size_t first, size_t n)
+{
+    const size_t i = first + (size_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n) return;
+    const float z = in[3 * i + 2];
+    if (U16) static_cast<uint16_t*>(out)[i] = depth_to_u16(z);
+    else static_cast<float*>(out)[i] = z;
+}
 }  // namespace
 
 // vector forms need 16-byte aligned pointers, and for a batch frames that start on 16-byte boundaries (W*H % 4 == 0)
@@ -553,6 +608,30 @@ int launch_widen_u16(const uint16_t* src, float* dst, size_t n, hipStream_t s)
                            reinterpret_cast<float4*>(dst), n8, src + n8 * 8, dst + n8 * 8, (unsigned)(n - n8 * 8));
     } else {
         hipLaunchKernelGGL(widen_u16_scalar_kernel, dim3(grid_for(n)), dim3(kThreads), 0, s, src, dst, n);
+    }
+    KDE_HIP_TRY(hipGetLastError());
+    return KDE_OK;
+}
+
+int launch_points_to_depth(const kde_float3* pts, void* out, size_t n, bool u16, hipStream_t s)
+{
+    if (n == 0) return KDE_OK;
+    const float* in = reinterpret_cast<const float*>(pts);
+    // vector form: whole groups of 8 points when both pointers are 16-byte aligned; the last n % 8 points, or everything
+    // otherwise, go through the scalar form
+    const size_t groups = aligned(pts, 16) && aligned(out, 16) ? n / 8 : 0;
+    const bool streaming = n * (12 + (u16 ? 2 : 4)) > kCacheBytes;
+    if (groups) {
+        const dim3 grid(grid_for(groups)), block(kThreads);
+        if (u16 && streaming) hipLaunchKernelGGL((points_to_depth_kernel<true, true>), grid, block, 0, s, groups, in, out);
+        else if (u16) hipLaunchKernelGGL((points_to_depth_kernel<false, true>), grid, block, 0, s, groups, in, out);
+        else if (streaming) hipLaunchKernelGGL((points_to_depth_kernel<true, false>), grid, block, 0, s, groups, in, out);
+        else hipLaunchKernelGGL((points_to_depth_kernel<false, false>), grid, block, 0, s, groups, in, out);
+    }
+    const size_t done = groups * 8;
+    if (done < n) {
+        if (u16) hipLaunchKernelGGL(points_to_depth_scalar_kernel<true>, dim3(grid_for(n - done)), dim3(kThreads), 0, s, in, out, done, n);
+        else hipLaunchKernelGGL(points_to_depth_scalar_kernel<false>, dim3(grid_for(n - done)), dim3(kThreads), 0, s, in, out, done, n);
     }
     KDE_HIP_TRY(hipGetLastError());
     return KDE_OK;

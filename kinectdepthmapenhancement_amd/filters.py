@@ -58,15 +58,16 @@ def _K9(K) -> np.ndarray:
 
 class _Handle:
     _destroy = None
+    _handle_type = C.c_void_p       # the ctypes type of the handle (a subclass where _native declares one)
 
     def __init__(self):
-        self._h = C.c_void_p()
+        self._h = self._handle_type()
         self._owner_lib = lib()     # a handle is destroyed by the library that created it
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
             getattr(self._owner_lib, self._destroy)(self._h)
-            self._h = C.c_void_p()
+            self._h = self._handle_type()
 
     def __del__(self):
         try:
@@ -726,7 +727,8 @@ class KinectDepthEnhancement(_Handle):
     """KinectDepthEnhancement.h: the reference's "PROPOSED" method (main.cpp:198-202).  Process = JointBilateralFilter,
     projectiveToReal, NormalMapGenerator (CM), NormalAdaptiveSuperpixel (10, 50, 50, 150, 1), LabelEquivalenceSeg and the
     five-argument PlaneProjection (KinectDepthEnhancement.cpp:56-81).  getRefinedDepth_* is not built: it returns a buffer
-    Process never writes."""
+    Process never writes; points_to_depth(getOptimizedPoints_Device()) is the enhanced depth map, and
+    KinectDepthEnhancementFeed runs Process on frames in host memory and returns it in the sensor's own format."""
     _destroy = "kde_enh_destroy"
 
     def __init__(self, width: int, height: int, max_batch: int = 1):
@@ -777,6 +779,81 @@ class KinectDepthEnhancement(_Handle):
 
     def getEdgeEnhanced3DPoints_Device(self) -> torch.Tensor:
         return self._get("kde_enh_edge_enhanced_points_device", (3,), torch.float32)
+
+
+_U16 = getattr(torch, "uint16", None)     # torch builds before 2.3 have no uint16
+
+
+def points_to_depth(points: torch.Tensor, out: Optional[torch.Tensor] = None, dtype=torch.float32) -> torch.Tensor:
+    """kde_points_to_depth on torch's current stream: the z of packed points [..., 3] (CUDA float32, contiguous) as a depth
+    map of shape points.shape[:-1].  dtype torch.float32 copies the bits of z; torch.uint16 gives the sensor's format
+    (millimetres rounded half to even, 0 = invalid: NaN, +-inf, z < 0.5, z >= 65535.5).  Where the torch build has no
+    uint16 (before 2.3), pass dtype=torch.int16: the result is an int16 tensor holding the uint16 bits
+    (`.cpu().numpy().view(numpy.uint16)`); an int16 `out` is accepted as such a view on every build."""
+    if not isinstance(points, torch.Tensor) or not points.is_cuda:
+        raise TypeError("points: expected a CUDA tensor")
+    if points.dtype != torch.float32 or points.dim() < 1 or points.shape[-1] != 3 or not points.is_contiguous():
+        raise ValueError(f"points: expected contiguous torch.float32 [..., 3], got {points.dtype} {tuple(points.shape)}")
+    if dtype == torch.float32:
+        fmt, store = _native.KDE_DEPTH_F32, (torch.float32,)
+    elif dtype is not None and dtype in (_U16, torch.int16):
+        fmt, store = _native.KDE_DEPTH_U16, tuple(t for t in (_U16, torch.int16) if t is not None)
+    else:
+        raise ValueError(f"dtype: expected torch.float32 or torch.uint16, got {dtype}")
+    shape = tuple(points.shape[:-1])
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=points.device)
+    elif not isinstance(out, torch.Tensor) or not out.is_cuda:
+        raise TypeError("out: expected a CUDA tensor")
+    elif out.dtype not in store or tuple(out.shape) != shape or not out.is_contiguous() or out.device != points.device:
+        raise ValueError(f"out: expected contiguous {store[0]} {shape} on {points.device}, got {out.dtype} {tuple(out.shape)}")
+    with torch.cuda.device(points.device):
+        check(lib().kde_points_to_depth(out.numel(), points.data_ptr(), fmt, out.data_ptr(), _stream()))
+    return out
+
+
+class KinectDepthEnhancementFeed(_Handle):
+    """Host-fed KinectDepthEnhancement::Process (kde_enh_feed_*): frames in host memory in, the enhanced result in host
+    memory out, in chunks of `chunk_frames` <= enh.max_batch (default: enh.max_batch) with the copies overlapped with the
+    kernels.  Borrows `enh` (kept alive by this object) and RUNS it: afterwards enh's getters show the last chunk of the
+    last call, and `enh` must not be used while process() runs.  SetParametor must have been called on `enh`.  A blocking
+    call on the feed's own streams, not on torch's current stream."""
+    _destroy = "kde_enh_feed_destroy"
+    _handle_type = _native.EnhFeedHandle
+    _OUTPUTS = {"points": (_native.KDE_OUT_POINTS_F32, np.float32, (3,)), "depth": (_native.KDE_OUT_DEPTH_F32, np.float32, ()),
+                "depth_u16": (_native.KDE_OUT_DEPTH_U16, np.uint16, ())}
+
+    def __init__(self, enh: KinectDepthEnhancement, chunk_frames: Optional[int] = None):
+        super().__init__()
+        self.enh = enh
+        self.Width, self.Height = enh.width, enh.height
+        self.chunk_frames = enh.max_batch if chunk_frames is None else chunk_frames
+        check(lib().kde_enh_feed_create(C.byref(self._h), enh._h, self.chunk_frames))
+
+    def process(self, depth, color, out=None, output: str = "points"):
+        """depth [n,H,W] float32 or uint16 (mm, 0 = invalid), color [n,H,W,3] uint8 BGR; numpy arrays or CPU torch tensors,
+        pinned or pageable.  output = "points" ([n,H,W,3] float32: the optimized cloud), "depth" ([n,H,W] float32: its z) or
+        "depth_u16" ([n,H,W] uint16: its z as the sensor's format).  out: a host buffer of that shape and type (a numpy
+        array is allocated when None).  Returns out."""
+        if output not in self._OUTPUTS:
+            raise ValueError(f"output: expected one of {sorted(self._OUTPUTS)}, got {output!r}")
+        ofmt, odt, trailing = self._OUTPUTS[output]
+        n = depth.shape[0] if len(depth.shape) == 3 else -1
+        dptr, ddt = _host_array(depth, (np.float32, np.uint16), (n, self.Height, self.Width), "depth")
+        cptr, _ = _host_array(color, (np.uint8,), (n, self.Height, self.Width, 3), "color")
+        if out is None:
+            out = np.empty((n, self.Height, self.Width) + trailing, odt)
+        optr, _ = _host_array(out, (odt,), (n, self.Height, self.Width) + trailing, "out")
+        fmt = _native.KDE_DEPTH_U16 if ddt == np.uint16 else _native.KDE_DEPTH_F32
+        check(lib().kde_enh_feed_process(self._h, n, dptr, fmt, cptr, ofmt, optr))
+        cf = min(self.chunk_frames, n)
+        self.enh._n = n - (-(-n // cf) - 1) * cf        # enh's getters now show the last chunk
+        return out
+
+    def last_stats(self) -> dict:
+        st = _native.FeedStats()
+        check(lib().kde_enh_feed_last_stats(self._h, C.byref(st)))
+        return {name: getattr(st, name) for name, _ in st._fields_}
 
 
 class EdgeRefinedSuperpixel(_Handle):
