@@ -16,6 +16,7 @@
 //   kde::JointBilateralFilterFeed (extension: JointBilateralFilter on frames in host memory, main.cpp:160-163)
 //   kde::KinectDepthEnhancementFeed, kde::pointsToDepth (extension: KinectDepthEnhancement on frames in host memory,
 //                                 main.cpp:160-163, 198-202, with the result as a point cloud or a depth map)
+//   kde::MeanError3D              (extension: the quality figure of main.cpp:220-308 for a batch, on the device)
 //
 // What differs from the reference headers, and why:
 //   * cv::gpu::GpuMat parameters are templates over "anything with .data/.rows/.cols/.step" — a real
@@ -1071,6 +1072,58 @@ private:
     static int out_format(const float*) { return KDE_OUT_DEPTH_F32; }
     static int out_format(const uint16_t*) { return KDE_OUT_DEPTH_U16; }
     kde_enh_feed* f_ = nullptr;
+};
+
+// extension (no reference counterpart as a class): the mean 3-D error of main.cpp:220-308 for n frames and up to eight candidate
+// results against one ground truth, computed on the device (kde_error3d_*).  A source is a cloud (float3*) or a depth map
+// (float* / uint16_t*, projected with the camera of setCamera as projectiveToReal(float*) would); compare() is asynchronous
+// on the object's stream and capturable; results_Host() synchronises.  The table is [n][m] records of (sum, count, mean).
+class MeanError3D {
+public:
+    MeanError3D(int width, int height, int max_batch = 1, int max_candidates = 8)
+    {
+        check(kde_error3d_create(&h_, width, height, max_batch, max_candidates));
+    }
+    ~MeanError3D() { kde_error3d_destroy(h_); }
+    MeanError3D(const MeanError3D&) = delete;
+    MeanError3D& operator=(const MeanError3D&) = delete;
+
+    static kde_error3d_source source(const float3* points_device) { return {points_device, KDE_SRC_POINTS_F32}; }
+    static kde_error3d_source source(const kde_float3* points_device) { return {points_device, KDE_SRC_POINTS_F32}; }
+    static kde_error3d_source source(const float* depth_device) { return {depth_device, KDE_SRC_DEPTH_F32}; }
+    static kde_error3d_source source(const uint16_t* depth_device) { return {depth_device, KDE_SRC_DEPTH_U16}; }
+
+    template <class MatLike>
+    void setCamera(const MatLike& intrinsic)
+    {
+        double k[9];
+        intrinsic_to_array(intrinsic, k);
+        check(kde_error3d_set_camera(h_, k));
+    }
+    void setRange(float z_min, float z_max) { check(kde_error3d_set_range(h_, z_min, z_max)); }
+    // n frames, m candidates (a host array of m descriptors) against truth; truth_frames = 1 (one truth for every frame) or n
+    void compare(int n, int m, const kde_error3d_source* candidates, const kde_error3d_source& truth, int truth_frames = 1)
+    {
+        check(kde_error3d_compare_batch(h_, n, m, candidates, &truth, truth_frames, stream_));
+    }
+    kde_error3d_result* results_Device() const
+    {
+        kde_error3d_result* p = nullptr;
+        check(kde_error3d_results_device(h_, &p));
+        return p;
+    }
+    const kde_error3d_result* results_Host() const
+    {
+        const kde_error3d_result* p = nullptr;
+        check(kde_error3d_results_host(h_, stream_, &p));
+        return p;
+    }
+    void setStream(void* hip_stream) { stream_ = hip_stream; }
+    kde_error3d* handle() const { return h_; }
+
+private:
+    kde_error3d* h_ = nullptr;
+    void* stream_ = nullptr;
 };
 
 }  // namespace kde

@@ -565,6 +565,54 @@ int kde_enh_feed_process(kde_enh_feed* f, int n, const void* depth_host, int dep
 /* what the last kde_enh_feed_process did (zeros before the first call) */
 int kde_enh_feed_last_stats(kde_enh_feed* f, kde_feed_stats* out);
 
+/* ============================================================================================
+ * MeanError3D — the reference's quality figure (main.cpp:220-308): the mean 3-D distance of each method's cloud from the
+ * cloud of the temporally averaged depth, over the pixels where both are valid.  One call compares m <= 8 candidate
+ * results with one ground truth for n frames on the device and leaves a table of (sum, count, mean) per frame and
+ * candidate.  For a candidate point p and the truth point t of the same pixel:
+ *   valid  iff p.z > z_min && p.z < z_max && t.z > z_min && t.z < z_max (both ends exclusive; NaN and +-inf are invalid;
+ *          defaults 50 and 15000, main.cpp:227-238)
+ *   term   dz = p.z - t.z, dy = p.y - t.y, dx = p.x - t.x; e = sqrtf((dz*dz + dy*dy) + dx*dx) in float32, no fused
+ *          multiply-add, correctly rounded sqrtf (main.cpp:240-242).  Nothing else is special: a valid z with a NaN x gives
+ *          a NaN term, which reaches the sum as it would in the reference.
+ *   count  the number of valid pixels; sum = the sum of their terms in BINARY64 in a fixed order;
+ *          mean = (float)(sum / (double)count), NaN when count == 0 like the reference's 0.0f / 0 (main.cpp:304-308).
+ * The reference accumulates in float32 in raster order (exact only to about count * 2^-24, and no parallel order can
+ * reproduce it); the binary64 sum here is within count * 2^-53 of the exact sum, and the table is deterministic to the bit:
+ * it does not depend on n, m, a frame's position in the batch, a candidate's position among the m, or pointer alignment.
+ * A source is a cloud or a depth map; a depth map (float, or uint16 widened by (float)u) stands for the cloud that
+ * projectiveToReal(float*) makes of it with the object's camera, and gives the bits the float3 source of that cloud gives.
+ * ========================================================================================== */
+enum { KDE_SRC_POINTS_F32 = 0, KDE_SRC_DEPTH_F32 = 1, KDE_SRC_DEPTH_U16 = 2 };
+typedef struct kde_error3d_source { const void* data_dev; int format; } kde_error3d_source;   /* [frames][H][W] of float3 / float / uint16 */
+typedef struct kde_error3d_result { double sum; uint32_t count; float mean; } kde_error3d_result;   /* 16 bytes */
+typedef struct kde_error3d kde_error3d;
+/* the accumulators of the loop main.cpp:220-308 (declared at :217-218) for max_batch frames x max_candidates (1..8)
+ * methods, on the current device.  On a
+ * host without a device the object is created without buffers: every call validates as usual and
+ * kde_error3d_compare_batch then returns KDE_ERR_HIP. */
+int kde_error3d_create(kde_error3d** out, int width, int height, int max_batch, int max_candidates);
+int kde_error3d_destroy(kde_error3d* h);   /* main.cpp:220-308 keeps its accumulators on the stack; NULL is a no-op */
+/* the camera a depth-map source is projected with (main.cpp:220-308 reads clouds made by convertor.projectiveToReal, :168):
+ * fx, fy as float, cx, cy truncated to int, like kde_dimconv_set_camera.  Needed only when a source is a depth map. */
+int kde_error3d_set_camera(kde_error3d* h, const double* K9);
+/* the validity range of main.cpp:220-308 (its literals 50.0f and 15000.0f): finite, z_min < z_max */
+int kde_error3d_set_range(kde_error3d* h, float z_min, float z_max);
+/* the loop of main.cpp:220-308 for n <= max_batch frames and m <= max_candidates candidates against one truth:
+ * `candidates` is a HOST array of m descriptors, read at call time (they travel as kernel arguments); truth_frames == 1
+ * compares every frame with the same truth frame, truth_frames == n frame f with truth frame f.  Pointers need the
+ * alignment of their element only (4 bytes for float3 and float, 2 for uint16); frames that start on 16-byte boundaries
+ * are read with 16-byte loads.  A depth-map source before kde_error3d_set_camera is KDE_ERR_INVALID.  Two launches, no
+ * allocation, no host synchronisation, no upload: capturable like kde_enh_process_batch. */
+int kde_error3d_compare_batch(kde_error3d* h, int n, int m, const kde_error3d_source* candidates,
+                              const kde_error3d_source* truth, int truth_frames, void* stream);
+/* the five averages of main.cpp:220-308 and what they were divided from: object-owned, [n][m] of the last call, valid until
+ * the next call or destroy.  KDE_ERR_INVALID before the first call. */
+int kde_error3d_results_device(kde_error3d* h, kde_error3d_result** out);
+/* the same in pinned host memory after a blocking copy on `stream` (main.cpp:220-308 computes on the host): synchronises,
+ * like the other *_host getters */
+int kde_error3d_results_host(kde_error3d* h, void* stream, const kde_error3d_result** out);
+
 #ifdef __cplusplus
 }
 #endif

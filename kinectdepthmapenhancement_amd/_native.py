@@ -31,6 +31,7 @@ class JbfParams(C.Structure):
 
 KDE_DEPTH_F32, KDE_DEPTH_U16 = 0, 1
 KDE_OUT_POINTS_F32, KDE_OUT_DEPTH_F32, KDE_OUT_DEPTH_U16 = 0, 1, 2
+KDE_SRC_POINTS_F32, KDE_SRC_DEPTH_F32, KDE_SRC_DEPTH_U16 = 0, 1, 2
 KDE_NORMALS_SDC, KDE_NORMALS_CM, KDE_NORMALS_BILATERAL = 0, 1, 2
 
 
@@ -62,6 +63,21 @@ class EnhFeedHandle(C.c_void_p):
     and refuses a plain c_void_p (any other handle) with a TypeError.  It also keeps the kde_enh_feed_* entry points out of
     the frozen record tools/abi_refusals.py enumerates (first argument c_void_p or POINTER(c_void_p)); their refusals are
     recorded by tools/abi_refusals_new.py instead."""
+
+
+class Error3dHandle(C.c_void_p):
+    """kde_error3d*: a ctypes type of its own, like EnhFeedHandle, which keeps the kde_error3d_* entry points out of the
+    frozen record tools/abi_refusals.py enumerates; tests/test_error3d_abi.py checks their refusals."""
+
+
+class Error3dSource(C.Structure):
+    """kde_error3d_source: a device pointer to [frames][H][W] elements and their KDE_SRC_* format."""
+    _fields_ = [("data_dev", C.c_void_p), ("format", C.c_int)]
+
+
+class Error3dResult(C.Structure):
+    """kde_error3d_result (16 bytes): the binary64 sum of the terms, the number of valid pixels, (float)(sum / count)."""
+    _fields_ = [("sum", C.c_double), ("count", C.c_uint32), ("mean", C.c_float)]
 
 
 def build(force: bool = False) -> str:
@@ -227,6 +243,13 @@ SIGNATURES = {
     "kde_enh_feed_destroy": (_i, [EnhFeedHandle]),
     "kde_enh_feed_process": (_i, [EnhFeedHandle, _i, _vp, _i, _vp, _i, _vp]),
     "kde_enh_feed_last_stats": (_i, [EnhFeedHandle, C.POINTER(FeedStats)]),
+    "kde_error3d_create": (_i, [C.POINTER(Error3dHandle), _i, _i, _i, _i]),
+    "kde_error3d_destroy": (_i, [Error3dHandle]),
+    "kde_error3d_set_camera": (_i, [Error3dHandle, _vp]),
+    "kde_error3d_set_range": (_i, [Error3dHandle, _f, _f]),
+    "kde_error3d_compare_batch": (_i, [Error3dHandle, _i, _i, C.POINTER(Error3dSource), C.POINTER(Error3dSource), _i, _vp]),
+    "kde_error3d_results_device": (_i, [Error3dHandle, _pp]),
+    "kde_error3d_results_host": (_i, [Error3dHandle, _vp, _pp]),
 }
 
 

@@ -66,6 +66,74 @@ __device__ __forceinline__ uint32_t fastdiv24(uint32_t x, const FastDiv24& f)
     return f.ok ? (uint32_t)(((uint64_t)x * f.m) >> f.sh) : x / f.d;
 }
 
+// DimensionConvertor's camera (DimensionConvertor.cpp:3-13): cx, cy truncated to int as the reference stores them
+struct Camera {
+    float fx, fy;
+    int cx, cy;
+    int width, height;
+};
+
+// ---- DimensionConvertor: projectiveToReal of one pixel ------------------------------------------------------------------
+// One function for stream_kernels.hip (K2) and error3d_kernels.hip (a depth-map source of the quality metric), so that a
+// term computed from a depth map has the bits the float3 cloud of that map would give.
+__device__ __forceinline__ void convert_ptr(float& x, float& y, float z, const Camera& c)
+{
+    // DimensionConvertor.h:34-48 — subtract, divide, multiply (in that order)
+    y = (float)c.cy - y;
+    x = x - (float)c.cx;
+    x /= c.fx;
+    y /= c.fy;
+    x *= z;
+    y *= z;
+}
+
+__device__ __forceinline__ void p2r_one(const Camera& c, int interp, unsigned x, unsigned y, float z, float* r)
+{
+    float fx_, fy_;
+    if (!interp) {
+        // convert_ptr(tuple<float,int>), DimensionConvertor.h:51-62
+        fy_ = (float)(int)y;
+        fx_ = (float)(int)x;
+        convert_ptr(fx_, fy_, z, c);
+    } else {
+        // convert_ptr_int, DimensionConvertor.h:80-103 (half-pixel grid, index decomposed over 2*width)
+        fy_ = (float)(int)y;
+        fx_ = (float)(int)x;
+        fy_ = (float)c.cy - fy_ / 2.0f;
+        fx_ = fx_ / 2.0f - (float)c.cx;
+        fx_ /= c.fx;
+        fy_ /= c.fy;
+        fx_ *= z;
+        fy_ *= z;
+    }
+    r[0] = fx_;
+    r[1] = fy_;
+    r[2] = z;
+}
+
+// ---- packed float3 through LDS, streaming accesses (stream_kernels.hip, error3d_kernels.hip) ---------------------------------
+// A thread owns 4 pixels = 48 B of packed float3, which it could only load or store as three 16-byte
+// pieces 48 B apart.  Each wave therefore passes its 3 KB through LDS once, so that every global store
+// (and, for the float3 -> float3 maps, every load) instruction moves 64 consecutive float4 = 1 KB.
+// LDS instructions of one wave execute in issue order, so a wave-level compiler barrier is all that is
+// needed between the write and the transposed read.
+__device__ __forceinline__ void wave_exchange_fence() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
+
+// NT: streaming (non-temporal) loads and stores, used when the call moves more than the 256 MB Infinity Cache can
+// hold anyway (a batch); single frames keep default caching so that the next kernel of the chain reads them on-chip.
+typedef float s_v4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ float4 ld4(const float4* p, bool nt)
+{
+    if (!nt) return *p;
+    const s_v4 v = __builtin_nontemporal_load(reinterpret_cast<const s_v4*>(p));
+    return make_float4(v.x, v.y, v.z, v.w);
+}
+__device__ __forceinline__ void st4(float4* p, float4 v, bool nt)
+{
+    if (nt) __builtin_nontemporal_store(s_v4{v.x, v.y, v.z, v.w}, reinterpret_cast<s_v4*>(p));
+    else *p = v;
+}
+
 // Workgroups are dealt round-robin over the 8 XCDs, each with its own L2.  Mapping workgroup `lin` of `nblk` to the
 // tile xcd_band_id(lin, nblk) gives XCD k the k-th contiguous eighth of the (raster-ordered) tile list, so the halo
 // rows two neighbouring tiles share are fetched into one L2 instead of two.  Bijective for any nblk.

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/kde_hip.h"
+#include "kde_device_math.h" // Camera and the device functions more than one kernel file runs
 #include "kde_host_math.h"   // exp_zero_threshold, spatial_table, smallest_*_reaching (pure C++)
 
 namespace kde {
@@ -57,6 +58,7 @@ extern StageCtl g_stage;
 #define KDE_STAGE(...)
 #endif
 
+constexpr size_t kCacheBytes = (size_t)256 << 20;   // Infinity Cache: calls that move more than this stream past it (ld4 / st4)
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
@@ -168,11 +170,6 @@ struct MrfLaunch {
 };
 int launch_mrf(const MrfLaunch& a, hipStream_t s);
 
-struct Camera {
-    float fx, fy;
-    int cx, cy;
-    int width, height;
-};
 int launch_p2r_depth(const Camera& c, int n, const float* depth, kde_float3* out, hipStream_t s);
 int launch_p2r_points(const Camera& c, int n, const kde_float3* in, kde_float3* out, hipStream_t s);
 int launch_p2r_interp(const Camera& c, int n, const float* depth, kde_float3* out, hipStream_t s);
@@ -187,6 +184,28 @@ int launch_buf_update(kde_weighted_d* buf, const float* d, size_t n, int n_frame
 int launch_widen_u16(const uint16_t* src, float* dst, size_t n, hipStream_t s);
 // kde_points_to_depth: the z of n packed points as float (bits unchanged) or as uint16 (depth_to_u16, kde_device_math.h)
 int launch_points_to_depth(const kde_float3* pts, void* out, size_t n, bool u16, hipStream_t s);
+
+// MeanError3D (error3d_kernels.hip): the quality metric of main.cpp:220-308 for n frames x m candidates, two launches
+constexpr int kError3dMaxCandidates = 8;
+constexpr unsigned kError3dSegmentPixels = 2048;   // pixels one workgroup reduces to one partial: a constant of the build
+struct Error3dPartial {                            // one segment of one frame for one candidate
+    double sum;
+    uint32_t count, pad_;
+};
+inline unsigned error3d_segments(size_t frame_px) { return (unsigned)((frame_px + kError3dSegmentPixels - 1) / kError3dSegmentPixels); }
+struct Error3dLaunch {
+    int n, m;
+    const void* cand[kError3dMaxCandidates];       // [n][H][W] of the format's element
+    int cand_format[kError3dMaxCandidates];        // KDE_SRC_*
+    const void* truth;                             // [truth_frames][H][W]
+    int truth_format;
+    int truth_frames;                              // 1 or n
+    Camera cam;                                    // width, height always; fx, fy, cx, cy where a source is a depth map
+    float z_min, z_max;
+    Error3dPartial* partials;                      // [n][m][error3d_segments(W * H)]
+    kde_error3d_result* results;                   // [n][m]
+};
+int launch_error3d(const Error3dLaunch& a, hipStream_t s);
 
 struct DaspGeom {
     int width, height, rows, cols, wx, wy;

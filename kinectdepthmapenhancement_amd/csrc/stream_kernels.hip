@@ -25,70 +25,15 @@ inline unsigned grid_for(size_t items)
     return (unsigned)b;
 }
 
-constexpr size_t kCacheBytes = (size_t)256 << 20;   // Infinity Cache: calls that move more than this stream past it
-
 inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 // ---- DimensionConvertor ---------------------------------------------------------------------
-__device__ __forceinline__ void convert_ptr(float& x, float& y, float z, const Camera& c)
-{
-    // DimensionConvertor.h:34-48 — subtract, divide, multiply (in that order)
-    y = (float)c.cy - y;
-    x = x - (float)c.cx;
-    x /= c.fx;
-    y /= c.fy;
-    x *= z;
-    y *= z;
-}
+// convert_ptr / p2r_one (DimensionConvertor.h:34-103) are in kde_device_math.h: error3d_kernels.hip runs the same functions.
+
+// wave_exchange_fence and the ld4 / st4 streaming accesses are in kde_device_math.h as well.
 
 // Four pixels per thread: one float4 depth load, three float4 stores (48 B = 4 packed float3).
 // blockIdx.y = frame; the in-frame index is 32-bit so one division serves four pixels.
-__device__ __forceinline__ void p2r_one(const Camera& c, int interp, unsigned x, unsigned y, float z, float* r)
-{
-    float fx_, fy_;
-    if (!interp) {
-        // convert_ptr(tuple<float,int>), DimensionConvertor.h:51-62
-        fy_ = (float)(int)y;
-        fx_ = (float)(int)x;
-        convert_ptr(fx_, fy_, z, c);
-    } else {
-        // convert_ptr_int, DimensionConvertor.h:80-103 (half-pixel grid, index decomposed over 2*width)
-        fy_ = (float)(int)y;
-        fx_ = (float)(int)x;
-        fy_ = (float)c.cy - fy_ / 2.0f;
-        fx_ = fx_ / 2.0f - (float)c.cx;
-        fx_ /= c.fx;
-        fy_ /= c.fy;
-        fx_ *= z;
-        fy_ *= z;
-    }
-    r[0] = fx_;
-    r[1] = fy_;
-    r[2] = z;
-}
-
-// A thread owns 4 pixels = 48 B of packed float3 output, which it could only store as three 16-byte
-// pieces 48 B apart.  Each wave therefore passes its 3 KB through LDS once, so that every global store
-// (and, for the float3 -> float3 maps, every load) instruction moves 64 consecutive float4 = 1 KB.
-// LDS instructions of one wave execute in issue order, so a wave-level compiler barrier is all that is
-// needed between the write and the transposed read.
-__device__ __forceinline__ void wave_exchange_fence() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
-
-// NT: streaming (non-temporal) loads and stores, used when the call moves more than the 256 MB Infinity Cache can
-// hold anyway (a batch); single frames keep default caching so that the next kernel of the chain reads them on-chip.
-typedef float s_v4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 ld4(const float4* p, bool nt)
-{
-    if (!nt) return *p;
-    const s_v4 v = __builtin_nontemporal_load(reinterpret_cast<const s_v4*>(p));
-    return make_float4(v.x, v.y, v.z, v.w);
-}
-__device__ __forceinline__ void st4(float4* p, float4 v, bool nt)
-{
-    if (nt) __builtin_nontemporal_store(s_v4{v.x, v.y, v.z, v.w}, reinterpret_cast<s_v4*>(p));
-    else *p = v;
-}
-
 template <bool NT>
 __global__ __launch_bounds__(kThreads) void p2r_depth_kernel(Camera c, const float* __restrict__ depth_all,
                                                             float* __restrict__ out_all, int interp)

@@ -812,6 +812,136 @@ def points_to_depth(points: torch.Tensor, out: Optional[torch.Tensor] = None, dt
     return out
 
 
+class MeanError3D(_Handle):
+    """The reference's quality figure (main.cpp:220-308) on the device (kde_error3d_*): the mean 3-D distance of up to
+    `max_candidates` results from one ground truth over the pixels where both are valid, for up to `max_batch` frames in
+    one call.  A source is a cloud ([n,H,W,3] float32) or a depth map ([n,H,W] float32, or uint16 / int16 holding the
+    sensor's uint16), which stands for the cloud DimensionConvertor.projectiveToReal makes of it with the camera of
+    set_camera.  The table holds, per frame and candidate, the binary64 sum of the float32 terms, the number of valid
+    pixels and mean = float32(sum / count) (NaN when count is 0); it is deterministic to the bit."""
+    _destroy = "kde_error3d_destroy"
+    _handle_type = _native.Error3dHandle
+    RESULT_DTYPE = np.dtype([("sum", "<f8"), ("count", "<u4"), ("mean", "<f4")])
+
+    def __init__(self, width: int, height: int, max_batch: int = 1, max_candidates: int = 8):
+        super().__init__()
+        self.width, self.height, self.max_batch, self.max_candidates = width, height, max_batch, max_candidates
+        self._n = self._m = 0
+        check(lib().kde_error3d_create(C.byref(self._h), width, height, max_batch, max_candidates))
+
+    def set_camera(self, K) -> None:
+        k = _K9(K)
+        check(lib().kde_error3d_set_camera(self._h, k.ctypes.data))
+
+    def set_range(self, z_min: float, z_max: float) -> None:
+        check(lib().kde_error3d_set_range(self._h, z_min, z_max))
+
+    def _source(self, t, name: str):
+        """(kde_error3d_source, frames) of a contiguous CUDA tensor [f,H,W,3] float32 or [f,H,W] float32 / uint16 / int16"""
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise TypeError(f"{name}: expected a CUDA tensor")
+        hw = (self.height, self.width)
+        if t.dtype == torch.float32 and t.dim() == 4 and tuple(t.shape[1:]) == hw + (3,):
+            fmt = _native.KDE_SRC_POINTS_F32
+        elif t.dtype == torch.float32 and t.dim() == 3 and tuple(t.shape[1:]) == hw:
+            fmt = _native.KDE_SRC_DEPTH_F32
+        elif t.dtype in (torch.int16, _U16) and t.dim() == 3 and tuple(t.shape[1:]) == hw:
+            fmt = _native.KDE_SRC_DEPTH_U16
+        else:
+            raise ValueError(f"{name}: expected float32 [n,{hw[0]},{hw[1]},3] (points) or float32 / uint16 [n,{hw[0]},{hw[1]}] "
+                             f"(depth), got {t.dtype} {tuple(t.shape)}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name}: expected a contiguous tensor")
+        return _native.Error3dSource(t.data_ptr(), fmt), t.shape[0]
+
+    def compare(self, candidates, truth: torch.Tensor) -> None:
+        """candidates: a sequence of 1..max_candidates tensors of n frames each; truth: n frames or 1 (the same truth for
+        every frame).  Asynchronous on torch's current stream; no allocation, copy or synchronisation on the device."""
+        cands = list(candidates)
+        if not cands:
+            raise ValueError("candidates: expected at least one tensor")
+        srcs = (_native.Error3dSource * len(cands))()
+        n = None
+        for i, t in enumerate(cands):
+            srcs[i], frames = self._source(t, f"candidates[{i}]")
+            if n is not None and frames != n:
+                raise ValueError(f"candidates[{i}]: {frames} frames, candidates[0] has {n}")
+            n = frames
+        tsrc, tframes = self._source(truth, "truth")
+        check(lib().kde_error3d_compare_batch(self._h, n, len(cands), srcs, C.byref(tsrc), tframes, _stream()))
+        self._n, self._m = n, len(cands)
+
+    def results_device(self) -> torch.Tensor:
+        """the [n, m] table of the last compare as raw bytes [n, m, 16] (sum: float64, count: uint32, mean: float32), a view
+        of the object-owned buffer"""
+        p = C.c_void_p()
+        check(lib().kde_error3d_results_device(self._h, C.byref(p)))
+        return _view(p.value, (self._n, self._m, 16), torch.uint8, self)
+
+    def results_host(self) -> np.ndarray:
+        """the [n, m] table as a numpy structured array (RESULT_DTYPE); synchronises torch's current stream"""
+        p = C.c_void_p()
+        check(lib().kde_error3d_results_host(self._h, _stream(), C.byref(p)))
+        raw = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(self._n * self._m * 16,)).copy()
+        return raw.view(self.RESULT_DTYPE).reshape(self._n, self._m)
+
+
+COMPARE_METHODS = ("input", "jbf", "mrf", "rgbf", "kde")
+
+
+def compare_methods(depth: torch.Tensor, bgr: torch.Tensor, truth_depth: torch.Tensor, K, rows: int, cols: int,
+                    methods=COMPARE_METHODS) -> dict:
+    """The comparison of the reference's main.cpp on a batch: every method of `methods` on depth [n,H,W] float32 and bgr
+    [n,H,W,3] uint8 (main.cpp:159-202: INPUT, JointBilateralFilter, MarkovRandomField, RegionGrowingBilateralFilter and
+    KinectDepthEnhancement with rows x cols superpixels, each result as the cloud projectiveToReal makes of it), then the
+    mean 3-D error of each against the cloud of truth_depth ([n,H,W] or [1,H,W]) in ONE MeanError3D.compare call
+    (main.cpp:220-308).  Returns {name: results[n]} (MeanError3D.RESULT_DTYPE)."""
+    methods = tuple(methods)
+    unknown = [m for m in methods if m not in COMPARE_METHODS]
+    if unknown or not methods or len(set(methods)) != len(methods):
+        raise ValueError(f"methods: expected distinct names of {COMPARE_METHODS}, got {methods}")
+    if not isinstance(depth, torch.Tensor) or depth.dim() != 3:
+        raise ValueError("depth: expected a [n, H, W] tensor")
+    n, h, w = depth.shape
+    _req(depth, torch.float32, (n, h, w), "depth")
+    _req(bgr, torch.uint8, (n, h, w, 3), "bgr")
+    conv = DimensionConvertor()
+    conv.setCameraParameters(K, w, h)
+
+    def cloud(d):
+        return conv.projectiveToReal(d.reshape(n, h, w), torch.empty((n, h, w, 3), dtype=torch.float32, device=depth.device))
+
+    keep, cands = [], []          # the stage objects own some of the compared buffers: alive until the table is read
+    for name in methods:
+        if name == "input":
+            cands.append(cloud(depth))                                            # main.cpp:168
+        elif name == "jbf":
+            o = JointBilateralFilter(w, h, max_batch=n)
+            cands.append(cloud(o.process_batch(depth, bgr)))                      # :179-182
+        elif name == "mrf":
+            o = MarkovRandomField(w, h, max_batch=n)
+            cands.append(cloud(o.process_batch(depth, bgr, torch.empty_like(depth))))   # :186-189
+        elif name == "rgbf":
+            o = RegionGrowingBilateralFilter(w, h, max_batch=n)
+            o.SetParametor(rows, cols, K)
+            o.process_batch(depth, cloud(depth), bgr)                             # :193
+            cands.append(cloud(o.getRefinedDepth_Device()))                       # :196
+        else:
+            o = KinectDepthEnhancement(w, h, max_batch=n)
+            o.SetParametor(rows, cols, K)
+            o.process_batch(depth, bgr)                                           # :200
+            cands.append(o.getOptimizedPoints_Device().reshape(n, h, w, 3))       # :202
+        if name != "input":
+            keep.append(o)
+    err = MeanError3D(w, h, max_batch=n, max_candidates=len(methods))
+    err.set_camera(K)
+    err.compare(cands, truth_depth)                                               # the truth as a depth map: :175
+    table = err.results_host()
+    for o in keep + [err, conv]:
+        o.close()
+    return {name: table[:, i].copy() for i, name in enumerate(methods)}
+
+
 class KinectDepthEnhancementFeed(_Handle):
     """Host-fed KinectDepthEnhancement::Process (kde_enh_feed_*): frames in host memory in, the enhanced result in host
     memory out, in chunks of `chunk_frames` <= enh.max_batch (default: enh.max_batch) with the copies overlapped with the
