@@ -17,6 +17,7 @@
 //   kde::KinectDepthEnhancementFeed, kde::pointsToDepth (extension: KinectDepthEnhancement on frames in host memory,
 //                                 main.cpp:160-163, 198-202, with the result as a point cloud or a depth map)
 //   kde::MeanError3D              (extension: the quality figure of main.cpp:220-308 for a batch, on the device)
+//   kde::PointCloudXYZRGB         (extension: the coloured clouds of main.cpp:211-300 for a batch, compacted on the device)
 //
 // What differs from the reference headers, and why:
 //   * cv::gpu::GpuMat parameters are templates over "anything with .data/.rows/.cols/.step" — a real
@@ -1123,6 +1124,76 @@ public:
 
 private:
     kde_error3d* h_ = nullptr;
+    void* stream_ = nullptr;
+};
+
+// extension (no reference counterpart as a class): the output step of main.cpp:211-300 for n frames of one method, on the
+// device (kde_cloud_*): the organised float3 grid and the colour image become 16-byte XYZRGB records (PCL's PointXYZRGB
+// payload: x, y, z in metres with z negated, rgb packed), the valid ones (50 < z < 15000) compacted in raster order at the
+// start of each frame's slot of W * H records -- or, with params.organized, every pixel with NaNs where it is invalid.
+// A source is what MeanError3D::source describes.  build() is asynchronous on the object's stream and capturable; the *_Host
+// members synchronise.  include/kde/pcd_io.hpp writes the records as a PCD file.
+class PointCloudXYZRGB {
+public:
+    static kde_cloud_params defaultParams()
+    {
+        kde_cloud_params p{};
+        check(kde_cloud_default_params(&p));
+        return p;
+    }
+    PointCloudXYZRGB(int width, int height, int max_batch = 1) { check(kde_cloud_create(&h_, width, height, max_batch, nullptr)); }
+    PointCloudXYZRGB(int width, int height, int max_batch, const kde_cloud_params& params)
+    {
+        check(kde_cloud_create(&h_, width, height, max_batch, &params));
+    }
+    ~PointCloudXYZRGB() { kde_cloud_destroy(h_); }
+    PointCloudXYZRGB(const PointCloudXYZRGB&) = delete;
+    PointCloudXYZRGB& operator=(const PointCloudXYZRGB&) = delete;
+
+    template <class MatLike>
+    void setCamera(const MatLike& intrinsic)
+    {
+        double k[9];
+        intrinsic_to_array(intrinsic, k);
+        check(kde_cloud_set_camera(h_, k));
+    }
+    // n frames of `source` with bgr_frames = 1 (one image for every frame) or n packed BGR images; out_device == nullptr: the
+    // object-owned buffer
+    void build(int n, const kde_error3d_source& source, const uint8_t* bgr_device, int bgr_frames = 1,
+               kde_cloud_point* out_device = nullptr)
+    {
+        check(kde_cloud_build_batch(h_, n, &source, bgr_device, bgr_frames, out_device, stream_));
+    }
+    kde_cloud_point* points_Device() const
+    {
+        kde_cloud_point* p = nullptr;
+        check(kde_cloud_points_device(h_, &p));
+        return p;
+    }
+    uint32_t* counts_Device() const
+    {
+        uint32_t* p = nullptr;
+        check(kde_cloud_counts_device(h_, &p));
+        return p;
+    }
+    const uint32_t* counts_Host() const
+    {
+        const uint32_t* p = nullptr;
+        check(kde_cloud_counts_host(h_, stream_, &p));
+        return p;
+    }
+    // the frames packed tightly: frame f is the records offsets[f] .. offsets[f + 1] - 1
+    const kde_cloud_point* points_Host(const uint64_t** offsets) const
+    {
+        const kde_cloud_point* p = nullptr;
+        check(kde_cloud_points_host(h_, stream_, &p, offsets));
+        return p;
+    }
+    void setStream(void* hip_stream) { stream_ = hip_stream; }
+    kde_cloud* handle() const { return h_; }
+
+private:
+    kde_cloud* h_ = nullptr;
     void* stream_ = nullptr;
 };
 

@@ -613,6 +613,52 @@ int kde_error3d_results_device(kde_error3d* h, kde_error3d_result** out);
  * like the other *_host getters */
 int kde_error3d_results_host(kde_error3d* h, void* stream, const kde_error3d_result** out);
 
+/* ==========================================================================================
+ * PointCloudXYZRGB: the output step of main.cpp:211-300 on the device -- a method's organised float3 grid (millimetres) and
+ * the colour image become the coloured cloud the reference pushes into a pcl::PointCloud<pcl::PointXYZRGB>, for a batch of
+ * frames.  For pixel i in raster order with point p and colour bytes (b, g, r):
+ *   valid   iff p.z > z_min && p.z < z_max (both ends exclusive; NaN and +-inf are invalid)
+ *   record  x = p.x / divisor, y = p.y / divisor, z = negate_z ? -(p.z / divisor) : p.z / divisor (correctly rounded float
+ *           divisions), rgb = (r << 16) | (g << 8) | b: PCL's packed rgb, and the payload of a binary PCD file with
+ *           FIELDS x y z rgb
+ *   dense mode (organized == 0, what the reference does): the valid records of frame f, in raster order, are the first
+ *           count[f] records of the frame's slot, which starts at record f * W * H; the rest of the slot is NOT written
+ *   organised mode: W * H records per frame; an invalid pixel has x = y = z = NaN (0x7fc00000) and keeps its colour
+ * A source is what kde_error3d_source describes; a depth map gives the bytes the float3 source of its cloud gives.
+ * ========================================================================================== */
+typedef struct kde_cloud_point { float x, y, z; uint32_t rgb; } kde_cloud_point;             /* 16 bytes */
+typedef struct kde_cloud_params { float z_min, z_max, divisor; int negate_z; int organized; } kde_cloud_params;
+typedef struct kde_cloud kde_cloud;
+/* the literals of main.cpp:211-300: z_min 50, z_max 15000, divisor 1000, negate_z 1; organized 0 */
+int kde_cloud_default_params(kde_cloud_params* p);
+/* the clouds of main.cpp:211-300 (declared at :211-216) for max_batch frames on the current device; p == NULL: the defaults.
+ * z_min, z_max finite with z_min < z_max, divisor finite and > 0.  The object owns max_batch * W * H records for calls with
+ * out_dev == NULL.  On a host without a device the object is created without buffers: every call validates as usual and
+ * kde_cloud_build_batch then returns KDE_ERR_HIP. */
+int kde_cloud_create(kde_cloud** out, int width, int height, int max_batch, const kde_cloud_params* p);
+int kde_cloud_destroy(kde_cloud* h);   /* main.cpp:211-300 holds its clouds in shared pointers; NULL is a no-op */
+/* the camera a depth-map source is projected with (main.cpp:211-300 reads clouds made by convertor.projectiveToReal, :168),
+ * as kde_error3d_set_camera.  Needed only when the source is a depth map. */
+int kde_cloud_set_camera(kde_cloud* h, const double* K9);
+/* the loop of main.cpp:211-300 for n <= max_batch frames of one method: `src` is a HOST descriptor read at call time;
+ * bgr_dev is [bgr_frames][H][W][3] with bgr_frames == 1 (one image for every frame) or n; out_dev is [n][W * H] records on a
+ * 16-byte boundary, or NULL for the object-owned buffer.  The source needs the alignment of its element only; frames that
+ * start on 16-byte boundaries are read with 16-byte loads, with the same result.  Dense mode: three launches (count per
+ * segment, scan per frame, scatter); organised mode: a 4 * n-byte memset and one launch.  No allocation, no host
+ * synchronisation, no spinning between workgroups: capturable like kde_error3d_compare_batch. */
+int kde_cloud_build_batch(kde_cloud* h, int n, const kde_error3d_source* src, const uint8_t* bgr_dev, int bgr_frames,
+                          kde_cloud_point* out_dev, void* stream);
+/* the records of the last call of main.cpp:211-300's loop (out_dev of that call, or the object-owned buffer) and the number of
+ * valid pixels per frame, count[n]; valid until the next call or destroy.  KDE_ERR_INVALID before the first call. */
+int kde_cloud_points_device(kde_cloud* h, kde_cloud_point** out);
+int kde_cloud_counts_device(kde_cloud* h, uint32_t** out);   /* main.cpp:211-300: the sizes of its clouds, on the device */
+/* count[n] in pinned host memory after a blocking copy on `stream` (main.cpp:211-300: cloud->size()): synchronises */
+int kde_cloud_counts_host(kde_cloud* h, void* stream, const uint32_t** out);
+/* the clouds of main.cpp:211-300 in pinned host memory (allocated on first use), frames packed tightly: frame f is the
+ * records offsets[f] .. offsets[f + 1] - 1, offsets[n] the total.  Dense mode copies only the used records.  The buffer
+ * out_dev of the last call must still be alive.  Synchronises. */
+int kde_cloud_points_host(kde_cloud* h, void* stream, const kde_cloud_point** out, const uint64_t** offsets);
+
 #ifdef __cplusplus
 }
 #endif

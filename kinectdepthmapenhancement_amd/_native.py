@@ -80,6 +80,21 @@ class Error3dResult(C.Structure):
     _fields_ = [("sum", C.c_double), ("count", C.c_uint32), ("mean", C.c_float)]
 
 
+class CloudHandle(C.c_void_p):
+    """kde_cloud*: a ctypes type of its own, like Error3dHandle, which keeps the kde_cloud_* entry points out of the frozen
+    record tools/abi_refusals.py enumerates; tests/test_cloud_abi.py checks their refusals."""
+
+
+class CloudParams(C.Structure):
+    """kde_cloud_params (defaults = the literals of main.cpp:227-230: 50, 15000, 1000, negated z; dense)."""
+    _fields_ = [("z_min", C.c_float), ("z_max", C.c_float), ("divisor", C.c_float), ("negate_z", C.c_int), ("organized", C.c_int)]
+
+
+class CloudPoint(C.Structure):
+    """kde_cloud_point (16 bytes): x, y, z and PCL's packed rgb, (r << 16) | (g << 8) | b."""
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("z", C.c_float), ("rgb", C.c_uint32)]
+
+
 def build(force: bool = False) -> str:
     """Compile libkde_hip.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     if force:
@@ -250,6 +265,15 @@ SIGNATURES = {
     "kde_error3d_compare_batch": (_i, [Error3dHandle, _i, _i, C.POINTER(Error3dSource), C.POINTER(Error3dSource), _i, _vp]),
     "kde_error3d_results_device": (_i, [Error3dHandle, _pp]),
     "kde_error3d_results_host": (_i, [Error3dHandle, _vp, _pp]),
+    "kde_cloud_default_params": (_i, [C.POINTER(CloudParams)]),
+    "kde_cloud_create": (_i, [C.POINTER(CloudHandle), _i, _i, _i, C.POINTER(CloudParams)]),
+    "kde_cloud_destroy": (_i, [CloudHandle]),
+    "kde_cloud_set_camera": (_i, [CloudHandle, _vp]),
+    "kde_cloud_build_batch": (_i, [CloudHandle, _i, C.POINTER(Error3dSource), _vp, _i, _vp, _vp]),
+    "kde_cloud_points_device": (_i, [CloudHandle, _pp]),
+    "kde_cloud_counts_device": (_i, [CloudHandle, _pp]),
+    "kde_cloud_counts_host": (_i, [CloudHandle, _vp, _pp]),
+    "kde_cloud_points_host": (_i, [CloudHandle, _vp, _pp, _pp]),
 }
 
 

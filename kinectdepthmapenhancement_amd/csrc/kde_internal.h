@@ -207,6 +207,25 @@ struct Error3dLaunch {
 };
 int launch_error3d(const Error3dLaunch& a, hipStream_t s);
 
+// PointCloudXYZRGB (cloud_kernels.hip): the coloured cloud of main.cpp:211-300 for n frames, compacted in raster order
+constexpr unsigned kCloudSegmentPixels = 2048;     // pixels one workgroup counts and scatters: a constant of the build
+constexpr unsigned kCloudScanThreads = 256;        // segment counts one pass of the per-frame scan (C2) takes
+inline unsigned cloud_segments(size_t frame_px) { return (unsigned)((frame_px + kCloudSegmentPixels - 1) / kCloudSegmentPixels); }
+struct CloudLaunch {
+    int n;
+    const void* src;                               // [n][H][W] of the format's element
+    int format;                                    // KDE_SRC_*
+    const uint8_t* bgr;                            // [bgr_frames][H][W][3]
+    int bgr_frames;                                // 1 or n
+    Camera cam;                                    // width, height always; fx, fy, cx, cy where the source is a depth map
+    float z_min, z_max, divisor;
+    int negate_z, organized;
+    uint32_t* seg;                                 // [n][cloud_segments(W * H)]: counts after C1, offsets after C2 (dense mode)
+    uint32_t* counts;                              // [n]
+    kde_cloud_point* out;                          // [n][H][W] records, 16-byte aligned: frame f's slot starts at f * W * H
+};
+int launch_cloud(const CloudLaunch& a, hipStream_t s);
+
 struct DaspGeom {
     int width, height, rows, cols, wx, wy;
 };

@@ -812,6 +812,25 @@ def points_to_depth(points: torch.Tensor, out: Optional[torch.Tensor] = None, dt
     return out
 
 
+def _source_of(width: int, height: int, t, name: str):
+    """(kde_error3d_source, frames) of a contiguous CUDA tensor [f,H,W,3] float32 or [f,H,W] float32 / uint16 / int16"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise TypeError(f"{name}: expected a CUDA tensor")
+    hw = (height, width)
+    if t.dtype == torch.float32 and t.dim() == 4 and tuple(t.shape[1:]) == hw + (3,):
+        fmt = _native.KDE_SRC_POINTS_F32
+    elif t.dtype == torch.float32 and t.dim() == 3 and tuple(t.shape[1:]) == hw:
+        fmt = _native.KDE_SRC_DEPTH_F32
+    elif t.dtype in (torch.int16, _U16) and t.dim() == 3 and tuple(t.shape[1:]) == hw:
+        fmt = _native.KDE_SRC_DEPTH_U16
+    else:
+        raise ValueError(f"{name}: expected float32 [n,{hw[0]},{hw[1]},3] (points) or float32 / uint16 [n,{hw[0]},{hw[1]}] "
+                         f"(depth), got {t.dtype} {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name}: expected a contiguous tensor")
+    return _native.Error3dSource(t.data_ptr(), fmt), t.shape[0]
+
+
 class MeanError3D(_Handle):
     """The reference's quality figure (main.cpp:220-308) on the device (kde_error3d_*): the mean 3-D distance of up to
     `max_candidates` results from one ground truth over the pixels where both are valid, for up to `max_batch` frames in
@@ -837,22 +856,7 @@ class MeanError3D(_Handle):
         check(lib().kde_error3d_set_range(self._h, z_min, z_max))
 
     def _source(self, t, name: str):
-        """(kde_error3d_source, frames) of a contiguous CUDA tensor [f,H,W,3] float32 or [f,H,W] float32 / uint16 / int16"""
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise TypeError(f"{name}: expected a CUDA tensor")
-        hw = (self.height, self.width)
-        if t.dtype == torch.float32 and t.dim() == 4 and tuple(t.shape[1:]) == hw + (3,):
-            fmt = _native.KDE_SRC_POINTS_F32
-        elif t.dtype == torch.float32 and t.dim() == 3 and tuple(t.shape[1:]) == hw:
-            fmt = _native.KDE_SRC_DEPTH_F32
-        elif t.dtype in (torch.int16, _U16) and t.dim() == 3 and tuple(t.shape[1:]) == hw:
-            fmt = _native.KDE_SRC_DEPTH_U16
-        else:
-            raise ValueError(f"{name}: expected float32 [n,{hw[0]},{hw[1]},3] (points) or float32 / uint16 [n,{hw[0]},{hw[1]}] "
-                             f"(depth), got {t.dtype} {tuple(t.shape)}")
-        if not t.is_contiguous():
-            raise ValueError(f"{name}: expected a contiguous tensor")
-        return _native.Error3dSource(t.data_ptr(), fmt), t.shape[0]
+        return _source_of(self.width, self.height, t, name)
 
     def compare(self, candidates, truth: torch.Tensor) -> None:
         """candidates: a sequence of 1..max_candidates tensors of n frames each; truth: n frames or 1 (the same truth for
@@ -884,6 +888,83 @@ class MeanError3D(_Handle):
         check(lib().kde_error3d_results_host(self._h, _stream(), C.byref(p)))
         raw = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(self._n * self._m * 16,)).copy()
         return raw.view(self.RESULT_DTYPE).reshape(self._n, self._m)
+
+
+class PointCloudXYZRGB(_Handle):
+    """The output step of the reference (main.cpp:211-300) on the device (kde_cloud_*): a method's result and the colour
+    image become the coloured cloud the reference pushes into a pcl::PointCloud<pcl::PointXYZRGB>, for up to `max_batch`
+    frames in one call.  A source is a cloud ([n,H,W,3] float32, millimetres) or a depth map ([n,H,W] float32, or uint16 /
+    int16 holding the sensor's uint16), which stands for the cloud DimensionConvertor.projectiveToReal makes of it with the
+    camera of set_camera.  A pixel is valid iff z_min < z < z_max; its record is (x / divisor, y / divisor, -z / divisor,
+    (r << 16) | (g << 8) | b).  Dense mode (the default) leaves the valid records of frame f, in raster order, in the first
+    counts()[f] records of the frame's slot of W * H records and writes nothing behind them; organized=True writes every
+    pixel, the invalid ones as three NaNs with their colour."""
+    _destroy = "kde_cloud_destroy"
+    _handle_type = _native.CloudHandle
+    POINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("rgb", "<u4")])
+
+    def __init__(self, width: int, height: int, max_batch: int = 1, z_min: float = 50.0, z_max: float = 15000.0,
+                 divisor: float = 1000.0, negate_z: bool = True, organized: bool = False):
+        super().__init__()
+        self.width, self.height, self.max_batch, self.organized = width, height, max_batch, bool(organized)
+        self._n = 0
+        p = _native.CloudParams(z_min, z_max, divisor, int(bool(negate_z)), int(bool(organized)))
+        check(lib().kde_cloud_create(C.byref(self._h), width, height, max_batch, C.byref(p)))
+
+    @staticmethod
+    def default_params() -> "_native.CloudParams":
+        p = _native.CloudParams()
+        check(lib().kde_cloud_default_params(C.byref(p)))
+        return p
+
+    def set_camera(self, K) -> None:
+        k = _K9(K)
+        check(lib().kde_cloud_set_camera(self._h, k.ctypes.data))
+
+    def build(self, source: torch.Tensor, bgr: torch.Tensor, out: Optional[torch.Tensor] = None) -> None:
+        """source: n frames; bgr: uint8 [n,H,W,3] or [1,H,W,3] (one image for every frame); out: uint8 [n, H*W, 16] for the
+        records, or None for the object-owned buffer.  Asynchronous on torch's current stream; no allocation, copy or
+        synchronisation on the device."""
+        src, n = _source_of(self.width, self.height, source, "source")
+        if not isinstance(bgr, torch.Tensor) or bgr.dim() != 4 or bgr.shape[0] not in (1, n):
+            raise ValueError(f"bgr: expected [1 or {n},{self.height},{self.width},3] uint8")
+        _req(bgr, torch.uint8, (bgr.shape[0], self.height, self.width, 3), "bgr")
+        if out is not None:
+            _req(out, torch.uint8, (n, self.height * self.width, 16), "out")
+        check(lib().kde_cloud_build_batch(self._h, n, C.byref(src), bgr.data_ptr(), bgr.shape[0], _ptr(out), _stream()))
+        self._n = n
+
+    def counts(self) -> np.ndarray:
+        """the number of valid pixels per frame of the last build, uint32 [n]; synchronises torch's current stream"""
+        p = C.c_void_p()
+        check(lib().kde_cloud_counts_host(self._h, _stream(), C.byref(p)))
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint32)), shape=(self._n,)).copy()
+
+    def counts_device(self) -> torch.Tensor:
+        """the same on the device, as raw bytes [n, 4] (uint32), a view of the object-owned buffer"""
+        p = C.c_void_p()
+        check(lib().kde_cloud_counts_device(self._h, C.byref(p)))
+        return _view(p.value, (self._n, 4), torch.uint8, self)
+
+    def points_device(self) -> torch.Tensor:
+        """the records of the last build as raw bytes [n, H*W, 16] (POINT_DTYPE): `out` of that call or the object-owned
+        buffer.  In dense mode only the first counts()[f] records of frame f are defined."""
+        p = C.c_void_p()
+        check(lib().kde_cloud_points_device(self._h, C.byref(p)))
+        return _view(p.value, (self._n, self.height * self.width, 16), torch.uint8, self)
+
+    def points_host(self) -> list:
+        """one structured array (POINT_DTYPE) per frame: counts()[f] records in dense mode, H*W in organised mode;
+        synchronises torch's current stream"""
+        p, off = C.c_void_p(), C.c_void_p()
+        check(lib().kde_cloud_points_host(self._h, _stream(), C.byref(p), C.byref(off)))
+        offsets = np.ctypeslib.as_array(C.cast(off, C.POINTER(C.c_uint64)), shape=(self._n + 1,)).copy()
+        self.offsets = offsets
+        total = int(offsets[-1])
+        if total == 0:
+            return [np.empty(0, self.POINT_DTYPE) for _ in range(self._n)]
+        raw = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(total * 16,)).copy().view(self.POINT_DTYPE)
+        return [raw[int(offsets[f]):int(offsets[f + 1])] for f in range(self._n)]
 
 
 COMPARE_METHODS = ("input", "jbf", "mrf", "rgbf", "kde")
