@@ -10,7 +10,9 @@
 //   * weights live in the log2 domain: arg1 = log2(S_ij) - kc*cd, arg2 = arg1 - kd*(d_q - avg)^2, one
 //     v_exp_f32 per tap and pass; pass-1 arguments stay in registers for pass 2 (windows <= 7);
 //   * taps that are invalid (depth <= 50 mm or outside the image) cost no branch or select: the scalar kernels
-//     give them a bias of 0xFF000000 (-1.7e38, weight exactly 0), the packed kernels multiply their weight by
+//     give them a bias of 0xFF000000 (-1.7e38, weight exactly 0); the packed kernels stage them with depth 0 and the colour-code
+//     term -2^126 (kInvalidHBits): weight exactly 0 in the bodies without the colour rule, which therefore carry no validity
+//     factor (plain packed adds into the sums of weights), while the bodies with the colour rule multiply the weight by
 //     v = clamp(2 d) = 0 inside the accumulating fma;
 //   * the reference's "a factor that underflowed to exactly 0 is not multiplied in" rule (Q1) is decided
 //     on the ARGUMENT (integer colour distance / |d_q - avg|) against host-computed thresholds, so it does
@@ -40,6 +42,16 @@ constexpr float kBiasF = 8388608.0f + 262144.0f;
 // packed kernels: bits of the float -(2^24 - 2^18); as the accumulator of dot4(c, c, .) it gives the bits of -(2^24 - 2^18 + |c|^2)
 // (2^23 <= 2^24 - 2^18 + |c|^2 < 2^24: the sum stays in the mantissa field of one binade)
 constexpr uint32_t kNegHBits = 0xCB7C0000u;
+// packed kernels: h_q of an INVALID pixel (depth <= 50 mm or outside the image), -2^126 (about -FLT_MAX / 4).  It swallows every
+// colour term it meets (2 (2^23 + a.b), -(2^18 + |a|^2): all below 2^25 in magnitude) and stays finite, so
+//   bodies without the colour rule: -cd = -2^126 and a1 = fma(-2^126, kc, ls) <= -kc 2^126 + 24 < -8000 for every kc the tuned
+//     kernels serve (kc > 1e-34 > 2^-113, kMinKc below): v_exp_f32 returns exactly 0, in pass 2 as well (a2 <= a1) -- the tap
+//     leaves every sum by itself;
+//   bodies with it: m = clamp(-2^126 + cd_skip) = 0, a1 = fma(-2^126, kc * 0, ls) = ls, finite (-inf here would give NaN): the
+//     tap is removed by its validity factor v = clamp(2 d) = 0, as before.
+constexpr uint32_t kInvalidHBits = 0xFE800000u;
+constexpr double kMinKc = 1.0e-34;            // jbf_fast_supported: smaller kc (sigma_c above 8.49e16) runs the generic kernel
+static_assert(kMinKc * 0x1p126 > 8000.0, "the invalid-tap marker must drive exp2 to 0 for every kc served");
 constexpr double kScaleLog2 = 24.0;           // weights are summed at 2^24 scale (see the header comment)
 
 struct FastArgs {
@@ -251,6 +263,7 @@ __global__ __launch_bounds__(BX* BY) void jbf_fast_kernel(const FastArgs a)
 // the argument fma.
 // Per unit (= 2 taps), window 11, in 4-cycle issue slots (v_exp_f32 counts 2):
 //   pass 1: 2 v_dot4 + 2 v_exp + 7 packed (2 a.b + h, -cd, mask, mask*kc, arg fma, 2 accumulating fma)        = 13.3
+//           (the two masks only with the colour rule; without it the second accumulating fma is a packed add)
 //   pass 2: the same argument (7) + 2 v_exp + 8 packed (d-avg, *sd, T2-t^2, mask, t*mask, arg fma, 2 acc.)   = 19.3
 // (the select form of the Q1 rules cost 17 + 24: profiles/r01_sweep_k1_clamp_form.log has the A/B.  Until the colour code
 //  took its packed-fma form each tap paid a v_lshl_add_u32 of its own, (a.b << 1) + bias: 14.3 + 20.3; in a tile without
@@ -305,6 +318,19 @@ __device__ __forceinline__ uint32_t wave_reduce(uint32_t v, Op op)
     v = op(v, dpp_mov<0x142, 0xa>(v));     // row_bcast:15
     v = op(v, dpp_mov<0x143, 0xc>(v));     // row_bcast:31
     return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+}
+
+// Instances whose invalid taps get their weight 0 through the colour code (kInvalidHBits) and whose LDS planes are interleaved
+// by rows (EXPERIMENTS.md Part I item 14): the recomputing kernels up to window 21.  Left in the earlier form, because the
+// new one costs them an occupancy step or scratch (profiles/k1_invalid_taps_registers.md): the windows that keep their pass-1
+// arguments (5: 88 bytes of scratch; 7: 142 -> 193 VGPRs), windows >= 23 (128 -> 132 VGPRs with the colour rule), two pairs per
+// thread without the colour rule from window 17 on (122 -> 130 VGPRs at 17, 48 more bytes of scratch at 19 / 21), and window 9
+// with one pair and no colour rule (12 bytes of scratch under its 8-wave bound).
+constexpr bool pk_invalid_by_code(int win, int np, bool cache, bool cskip)
+{
+    if (cache || win > 21) return false;
+    if (!cskip && ((np == 2 && win >= 17) || (np == 1 && win == 9))) return false;
+    return true;
 }
 
 // second launch bound = waves per SIMD the register allocator must leave room for: the four rule-specialised bodies
@@ -364,9 +390,23 @@ void jbf_pk_kernel(const FastArgs a)
     constexpr int SEGP = NP + R;                      // aligned pairs in the row segment of a thread
     constexpr int HALF = (WIN - 1) / 2;
     static_assert(RA >= R && P % 2 == 0 && (!VL || ((RA + S1) % 4 == 0 && TW % 4 == 0 && (SH != 0 || P % 4 == 0))), "tile geometry");
+    // BYCODE instances (pk_invalid_by_code): ONE array, the three planes interleaved by rows: staged row ly = depth | colour | h_q,
+    // P dwords each, at ly * RP.  All the 64-bit pairs a thread reads in one window row then lie within 3 P dwords (< 2040 bytes) of
+    // ONE address register, inside the offset fields of ds_read2_b64.  (As three arrays the planes are 0x2150 bytes apart at window
+    // 11: beyond those fields, a v_add_u32 per plane and pair group in every row trip of this VALU-bound kernel.)  The others keep
+    // three arrays, RP = P.  The same number of bytes either way.
+    constexpr bool BYCODE = pk_invalid_by_code(WIN, NP, CACHE, CSKIP);
+    constexpr int RP = BYCODE ? 3 * P : P;
+    // (an array that an instance does not reference takes no LDS)
     __shared__ __attribute__((aligned(16))) float s_d[LH * P];
     __shared__ __attribute__((aligned(16))) uint32_t s_c[LH * P];
     __shared__ __attribute__((aligned(16))) float s_n[LH * P];            // h_q = -(2^24 - 2^18 + |b|^2), see unit_arg
+    __shared__ __attribute__((aligned(16))) uint32_t s_rows[3 * LH * P];  // BYCODE; h_q of an invalid pixel: -2^126
+    // l_d / l_c / l_n(ly * RP + column): the element of the plane, in whichever arrays the instance uses (constant conditions:
+    // only the chosen arrays are referenced)
+#define l_d(k) (*(BYCODE ? reinterpret_cast<float*>(s_rows) + (k) : s_d + (k)))
+#define l_c(k) (*(BYCODE ? s_rows + P + (k) : s_c + (k)))
+#define l_n(k) (*(BYCODE ? reinterpret_cast<float*>(s_rows) + 2 * P + (k) : s_n + (k)))
 
     const unsigned nblk = gridDim.x;
     const unsigned lin = blockIdx.x;
@@ -406,9 +446,10 @@ void jbf_pk_kernel(const FastArgs a)
                 c = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
             }
             const bool valid = d > 50.0f;
-            s_d[i] = valid ? d : 0.0f;
-            s_c[i] = c;
-            s_n[i] = __uint_as_float(dot4(c, c, kNegHBits));
+            const int li = ly * RP + lx;
+            l_d(li) = valid ? d : 0.0f;
+            l_c(li) = c;
+            l_n(li) = __uint_as_float((!BYCODE || valid) ? dot4(c, c, kNegHBits) : kInvalidHBits);
         }
     }
     for (int g = tid; VL && g < G * LH; g += NT) {
@@ -443,19 +484,19 @@ void jbf_pk_kernel(const FastArgs a)
         for (int k = 0; k < 4; k++) {
             const bool valid = d[k] > 50.0f;
             d[k] = valid ? d[k] : 0.0f;
-            nn[k] = __uint_as_float(dot4(c[k], c[k], kNegHBits));
+            nn[k] = __uint_as_float((!BYCODE || valid) ? dot4(c[k], c[k], kNegHBits) : kInvalidHBits);
         }
-        const int li = ly * P + 4 * gi + SH;
+        const int li = ly * RP + 4 * gi + SH;
         if constexpr (SH == 0) {
-            *reinterpret_cast<float4*>(&s_d[li]) = make_float4(d[0], d[1], d[2], d[3]);
-            *reinterpret_cast<uint4*>(&s_c[li]) = make_uint4(c[0], c[1], c[2], c[3]);
-            *reinterpret_cast<float4*>(&s_n[li]) = make_float4(nn[0], nn[1], nn[2], nn[3]);
+            *reinterpret_cast<float4*>(&l_d(li)) = make_float4(d[0], d[1], d[2], d[3]);
+            *reinterpret_cast<uint4*>(&l_c(li)) = make_uint4(c[0], c[1], c[2], c[3]);
+            *reinterpret_cast<float4*>(&l_n(li)) = make_float4(nn[0], nn[1], nn[2], nn[3]);
         } else {
 #pragma unroll
             for (int k = 0; k < 4; k++) {
-                s_d[li + k] = d[k];
-                s_c[li + k] = c[k];
-                s_n[li + k] = nn[k];
+                l_d(li + k) = d[k];
+                l_c(li + k) = c[k];
+                l_n(li + k) = nn[k];
             }
         }
     }
@@ -492,21 +533,21 @@ void jbf_pk_kernel(const FastArgs a)
             // element e = lane + 64 k of the region, row-major over its pairs: (row, pair, LDS index) advance by 64 elements per step
             constexpr int QY = 64 / RWP, QP = 64 % RWP;
             int ry = lane / RWP, rp = lane - ry * RWP;
-            int li = (ty0 + ry) * P + sxw + 2 * rp;
+            int li = (ty0 + ry) * RP + sxw + 2 * rp;
 #pragma unroll
             for (int k = 0; k < (NE + 63) / 64; k++) {
                 if (k > 0) {
                     const bool wrap = rp + QP >= RWP;
                     rp += wrap ? QP - RWP : QP;
                     ry += wrap ? QY + 1 : QY;
-                    li += wrap ? (QY + 1) * P + 2 * (QP - RWP) : QY * P + 2 * QP;
+                    li += wrap ? (QY + 1) * RP + 2 * (QP - RWP) : QY * RP + 2 * QP;
                 }
                 if (64 * k + 63 < NE || lane + 64 * k < NE) {
-                    const u2 d = *reinterpret_cast<const u2*>(&s_d[li]);
+                    const u2 d = *reinterpret_cast<const u2*>(&l_d(li));
                     dmin = min(dmin, min(d.x - 1u, d.y - 1u));
                     dmax = max(dmax, max(d.x, d.y));
                     if constexpr (CSKIP) {       // (instances without the colour rule need no colour statistics)
-                        const u2 c = *reinterpret_cast<const u2*>(&s_c[li]);
+                        const u2 c = *reinterpret_cast<const u2*>(&l_c(li));
                         uint32_t lo0 = c.x, lo1 = c.y, hi0 = c.x, hi1 = c.y;
                         if constexpr (MASKED) {      // pixels staged from outside the image (zeros) do not count
                             const bool iny = (unsigned)(gy0 + ry) < (unsigned)a.height;
@@ -572,7 +613,7 @@ void jbf_pk_kernel(const FastArgs a)
 #pragma unroll
         for (int h = 0; h < 2; h++) {
             const int k = 2 * pp + h;
-            cc[k] = s_c[(ty + R) * P + sx + R + k];
+            cc[k] = l_c((ty + R) * RP + sx + R + k);
             const uint32_t na = dot4(cc[k], cc[k], 0);
             negC[pp][h] = -((float)kOff + (float)na);
         }
@@ -588,7 +629,8 @@ void jbf_pk_kernel(const FastArgs a)
     // Q1 rules as packed arithmetic on {0,1} masks made by the clamp bit:
     //   colour: m = clamp(cd_skip - cd) is 1 for cd < cd_skip and 0 otherwise (integers), a1 = fma(-cd, kc*m, ls)
     //   depth:  q = T2 - t^2 (one rounding, sign exact), m = clamp(q * 2^100), a2 = fma(-(t*m), t, a1)
-    //   invalid taps: colour code and depth 0 stay finite, and the tap enters the sums with v = clamp(2 d) = 0
+    //   invalid taps: depth 0 and h_q = -2^126 (kInvalidHBits).  Without the colour rule the weight is exactly 0 by itself;
+    //   with it the argument stays finite and the tap enters the sums with v = clamp(2 d) = 0
     const f2 Tc = bcast((float)a.cd_skip);
     const f2 T2 = bcast(a.t2_skip);
     const f2 kBig = bcast(0x1p100f);
@@ -645,17 +687,18 @@ void jbf_pk_kernel(const FastArgs a)
     };
 
     auto pass1_row = [&](auto cs_tag, auto keep_tag, int i) {
+        constexpr bool VP = decltype(cs_tag)::value || !BYCODE;   // validity pairs: where an invalid tap's weight is not 0 by itself
         constexpr bool KEEP = decltype(keep_tag)::value;
-        f2 dp[SEGP], vp[SEGP];
+        f2 dp[SEGP], vp[VP ? SEGP : 1];       // validity pairs: only where the colour rule runs (kInvalidHBits)
         u2 cp[SEGP];
         f2 np[SEGP];
-        const int rb = (ty + i) * P + sx;
+        const int rb = (ty + i) * RP + sx;
 #pragma unroll
         for (int m = 0; m < SEGP; m++) {
-            dp[m] = ALIGNED ? *reinterpret_cast<const f2*>(&s_d[rb + 2 * m]) : f2{s_d[rb + 2 * m], s_d[rb + 2 * m + 1]};
-            cp[m] = ALIGNED ? *reinterpret_cast<const u2*>(&s_c[rb + 2 * m]) : u2{s_c[rb + 2 * m], s_c[rb + 2 * m + 1]};
-            np[m] = ALIGNED ? *reinterpret_cast<const f2*>(&s_n[rb + 2 * m]) : f2{s_n[rb + 2 * m], s_n[rb + 2 * m + 1]};
-            vp[m] = pk_add_clamp(dp[m], dp[m]);      // 1 for a valid tap (d > 50), 0 for d == 0
+            dp[m] = ALIGNED ? *reinterpret_cast<const f2*>(&l_d(rb + 2 * m)) : f2{l_d(rb + 2 * m), l_d(rb + 2 * m + 1)};
+            cp[m] = ALIGNED ? *reinterpret_cast<const u2*>(&l_c(rb + 2 * m)) : u2{l_c(rb + 2 * m), l_c(rb + 2 * m + 1)};
+            np[m] = ALIGNED ? *reinterpret_cast<const f2*>(&l_n(rb + 2 * m)) : f2{l_n(rb + 2 * m), l_n(rb + 2 * m + 1)};
+            if constexpr (VP) vp[m] = pk_add_clamp(dp[m], dp[m]);      // 1 for a valid tap (d > 50), 0 for d == 0
         }
 #pragma unroll
         for (int pp = 0; pp < NP; pp++) {
@@ -665,26 +708,28 @@ void jbf_pk_kernel(const FastArgs a)
                 if constexpr (KEEP) arg[(i * NP + pp) * WIN + u] = a1;
                 const f2 f = f2{__builtin_amdgcn_exp2f(a1.x), __builtin_amdgcn_exp2f(a1.y)};
                 wsum[pp] = pk_fma(unit_depth(dp, pp, u), f, wsum[pp]);
-                wgt[pp] = pk_fma(unit_depth(vp, pp, u), f, wgt[pp]);
+                if constexpr (VP) wgt[pp] = pk_fma(unit_depth(vp, pp, u), f, wgt[pp]);
+                else wgt[pp] = wgt[pp] + f;             // f == 0 for an invalid tap
             }
         }
     };
     f2 c2[NP], num[NP], den[NP];
 
     auto pass2_row = [&](auto cs_tag, auto ds_tag, auto keep_tag, int i) {
+        constexpr bool VP = decltype(cs_tag)::value || !BYCODE;   // validity pairs: where an invalid tap's weight is not 0 by itself
         constexpr bool DS = decltype(ds_tag)::value;
         constexpr bool KEEP = decltype(keep_tag)::value;
-        f2 dp[SEGP], vp[SEGP];
+        f2 dp[SEGP], vp[VP ? SEGP : 1];
         u2 cp[SEGP];
         f2 np[SEGP];
-        const int rb = (ty + i) * P + sx;
+        const int rb = (ty + i) * RP + sx;
 #pragma unroll
         for (int m = 0; m < SEGP; m++) {
-            dp[m] = ALIGNED ? *reinterpret_cast<const f2*>(&s_d[rb + 2 * m]) : f2{s_d[rb + 2 * m], s_d[rb + 2 * m + 1]};
-            vp[m] = pk_add_clamp(dp[m], dp[m]);
+            dp[m] = ALIGNED ? *reinterpret_cast<const f2*>(&l_d(rb + 2 * m)) : f2{l_d(rb + 2 * m), l_d(rb + 2 * m + 1)};
+            if constexpr (VP) vp[m] = pk_add_clamp(dp[m], dp[m]);
             if constexpr (!KEEP) {
-                cp[m] = ALIGNED ? *reinterpret_cast<const u2*>(&s_c[rb + 2 * m]) : u2{s_c[rb + 2 * m], s_c[rb + 2 * m + 1]};
-                np[m] = ALIGNED ? *reinterpret_cast<const f2*>(&s_n[rb + 2 * m]) : f2{s_n[rb + 2 * m], s_n[rb + 2 * m + 1]};
+                cp[m] = ALIGNED ? *reinterpret_cast<const u2*>(&l_c(rb + 2 * m)) : u2{l_c(rb + 2 * m), l_c(rb + 2 * m + 1)};
+                np[m] = ALIGNED ? *reinterpret_cast<const f2*>(&l_n(rb + 2 * m)) : f2{l_n(rb + 2 * m), l_n(rb + 2 * m + 1)};
             }
         }
 #pragma unroll
@@ -705,7 +750,8 @@ void jbf_pk_kernel(const FastArgs a)
                 }
                 const f2 f = f2{__builtin_amdgcn_exp2f(a2.x), __builtin_amdgcn_exp2f(a2.y)};
                 num[pp] = pk_fma(dq, f, num[pp]);
-                den[pp] = pk_fma(unit_depth(vp, pp, u), f, den[pp]);
+                if constexpr (VP) den[pp] = pk_fma(unit_depth(vp, pp, u), f, den[pp]);
+                else den[pp] = den[pp] + f;
             }
         }
     };
@@ -763,6 +809,10 @@ void jbf_pk_kernel(const FastArgs a)
         })
     }
 }
+
+#undef l_d
+#undef l_c
+#undef l_n
 
 template <int WIN, int NP, int BX, int BY, bool CACHE, bool VL, bool ELIDE_ON = true, int WTX = BX>
 int launch_pk_variant(const JbfLaunch& l, const FastArgs& fa, bool cskip, hipStream_t s)
@@ -883,7 +933,7 @@ bool jbf_fast_supported(const JbfLaunch& l)
 {
     if (l.color_sigma == 0.0f || l.depth_sigma == 0.0f) return false;
     const double kc = 1.4426950408889634 / (double)l.color_den;
-    if (!(kc * 1.0e38 > 1.0e4) || !(kc < 1.0e30)) return false;   // the invalid-tap bias must drive exp2 to 0
+    if (!(kc > kMinKc) || !(kc < 1.0e30)) return false;   // the invalid-tap bias / marker must drive exp2 to 0 (kInvalidHBits)
     return jbf_fast_default_variant(l) >= 0;
 }
 
