@@ -33,6 +33,12 @@ int kde_test_sqrt_int24(uint32_t first, uint32_t n, float* out_dev, void* stream
 int kde_test_fastdiv24(uint32_t d, uint64_t max_dividend, uint32_t n, const uint32_t* xs_dev, uint32_t* out_dev,
                        uint32_t* m_sh_ok, void* stream);
 
+/* The 256-way reduction tree of the superpixel cluster kernels (csrc/kde_superpixel_device.h, tree256<2, 2>) run by ONE
+ * 256-thread workgroup: thread t contributes iv_rows_dev[r * 256 + t] and fv_rows_dev[r * 256 + t] for r = 0, 1.
+ * out_dev (4 words) receives lane 0's results: the two integer sums (modulo 2^32), then the bits of the two float sums,
+ * whose value depends on the tree's order of additions.  0 = ok. */
+int kde_test_tree256(const int32_t* iv_rows_dev, const float* fv_rows_dev, uint32_t* out_dev, void* stream);
+
 /* ---- tools/hooks/libkde_hip_stage.so ------------------------------------------------------------------------------
  * The product library's own sources compiled with -DKDE_STAGE_HOOKS: every entry point of include/kde_hip.h (same
  * code, same flags) plus the one below.  It exists so that the parity tests can check K1 and K10 STAGE BY STAGE: the

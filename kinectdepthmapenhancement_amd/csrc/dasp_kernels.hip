@@ -12,6 +12,7 @@
 //   All grids are ceil-div and bounds-guarded (D4); out-of-buffer taps of K6 read colour 0 (D1).
 #include "kde_internal.h"
 #include "kde_device_math.h"
+#include "kde_superpixel_device.h"
 #include <type_traits>
 
 namespace kde {
@@ -162,34 +163,7 @@ struct CalcDivs {          // divisions of the assignment step by multiplication
     FastDiv24 wx, wy, cols;
 };
 
-// "take = d < best; best = take ? d : best; label = take ? id : label" compiles to one v_cmp and TWO back-to-back
-// v_cndmask_b32 in the VOP2 encoding (condition implicitly in VCC) -- and on gfx950 the second of two adjacent VOP2 v_cndmask
-// stalls the SIMD for ~20 cycles (tools/valu_microbench: "1 v_cmp + 2 v_cndmask (vcc)" 3.2-6.8 ns per instruction against
-// 1.3 with one other VALU instruction between them and 1.7 in the VOP3 encoding; profiles/r04_valu_microbench_vcc.txt).
-// The argmin update therefore keeps its condition in an SGPR pair and selects with the VOP3 form: same results, no stall.
-// (A 64-bit SGPR pair is the condition of a 64-wide wavefront: this library is built for gfx950 only, see the Makefile.)
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
-#error "dasp_kernels.hip: the SGPR-pair conditions below assume gfx950 (wave64); build with --offload-arch=gfx950"
-#endif
-__device__ __forceinline__ uint64_t lt_mask(float x, float y)
-{
-    uint64_t m;
-    asm("v_cmp_lt_f32_e64 %0, %1, %2" : "=s"(m) : "v"(x), "v"(y));
-    return m;
-}
-__device__ __forceinline__ float sel_f(uint64_t m, float a, float b)       // m ? a : b
-{
-    float r;
-    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(b), "v"(a), "s"(m));
-    return r;
-}
-__device__ __forceinline__ int sel_i(uint64_t m, int a, int b)
-{
-    int r;
-    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(b), "v"(a), "s"(m));
-    return r;
-}
-
+// (the argmin updates below keep their condition in an SGPR pair: lt_mask / sel_f / sel_i, kde_superpixel_device.h)
 template <int NS, bool USE_LDS, bool FIRST>
 __global__ __launch_bounds__(256) void calc_ld_kernel(DaspGeom g, const uint8_t* __restrict__ bgr,
                                                      const kde_float3* __restrict__ pts, CalcSets<NS> sets, float win2,
@@ -402,8 +376,6 @@ __global__ __launch_bounds__(256) void calc_ld_kernel(DaspGeom g, const uint8_t*
 }
 
 // ---- K8 analyzeClusters<256> (.cu:315-568) ---------------------------------------------------------
-__device__ __forceinline__ int f2i_rz(float v) { return (int)v; }   // v_cvt_i32_f32: RZ, saturating, NaN -> 0
-
 // One segmenter's view of analyzeClusters; blockIdx.z picks the segmenter (a pipeline updates both in one launch).
 // `labels` is the label map calculateLD writes next to its (distance, label) records -- the same labels at 4 bytes
 // per pixel, so one 16-byte access fetches four of them.
@@ -418,77 +390,31 @@ struct AnalyzeSets {
     int band;
 };
 
-// The tail of analyzeClusters (.cu:425-566): the reference's 256-way tree over the threads' partial sums (levels +128, +64
-// through LDS, +32 ... +1 inside the first wavefront) and the new cluster record.  si / sf: 7 x 256 ints and 3 x 256 floats of LDS.
-__device__ __forceinline__ void analyze_reduce_and_store(const DaspGeom& g, int tid, int cluster_id, int (*si)[256], float (*sf)[256],
-                                                         int r_, int g_, int b_, int x_, int y_, int s_, int n_, float xf, float yf,
-                                                         float zf, kde_superpixel* __restrict__ mean, kde_float3* __restrict__ centers,
-                                                         const float* __restrict__ intr)
+// The tail of analyzeClusters (.cu:425-566): the reference's 256-way tree over the threads' partial sums (tree256,
+// kde_superpixel_device.h) and the new cluster record.  iv: r g b x y size npoints, fv: X Y Z; buf: 10 x 256 words of LDS.
+__device__ __forceinline__ void analyze_reduce_and_store(const DaspGeom& g, int tid, int cluster_id, uint32_t (*buf)[256], int* iv,
+                                                         float* fv, kde_superpixel* __restrict__ mean,
+                                                         kde_float3* __restrict__ centers, const float* __restrict__ intr)
 {
-    si[0][tid] = r_; si[1][tid] = g_; si[2][tid] = b_; si[3][tid] = x_; si[4][tid] = y_;
-    si[5][tid] = s_; si[6][tid] = n_;
-    sf[0][tid] = xf; sf[1][tid] = yf; sf[2][tid] = zf;
-    __syncthreads();
-    // tree levels +128, +64 through LDS (.cu:425-454)
-    if (tid < 128) {
-#pragma unroll
-        for (int k = 0; k < 7; k++) si[k][tid] += si[k][tid + 128];
-#pragma unroll
-        for (int k = 0; k < 3; k++) sf[k][tid] += sf[k][tid + 128];
+    tree256<7, 3>(tid, buf, iv, fv);           // .cu:425-528
+    if (tid != 0 || iv[5] == 0) return;        // .cu:530-566
+    const int size = iv[5], np = iv[6];
+    const int mean_x = iv[3] / size, mean_y = iv[4] / size;
+    int pix_x = mean_x, pix_y = mean_y;
+    if (np != 0) {
+        const kde_float3 c = mean3(fv[0], fv[1], fv[2], np);
+        centers[cluster_id] = c;
+        reproject_centre(c, intr, g.width, g.height, mean_x, mean_y, pix_x, pix_y);   // sic, .cu:549
     }
-    __syncthreads();
-    if (tid < 64) {
-        int iv[7];
-        float fv[3];
-#pragma unroll
-        for (int k = 0; k < 7; k++) iv[k] = si[k][tid] + si[k][tid + 64];
-#pragma unroll
-        for (int k = 0; k < 3; k++) fv[k] = sf[k][tid] + sf[k][tid + 64];
-        // levels +32 ... +1 inside the wavefront (.cu:455-528); lane 0 sees the clean tree
-#pragma unroll
-        for (int step = 32; step >= 1; step >>= 1) {
-#pragma unroll
-            for (int k = 0; k < 7; k++) iv[k] += __shfl_down(iv[k], step, 64);
-#pragma unroll
-            for (int k = 0; k < 3; k++) fv[k] += __shfl_down(fv[k], step, 64);
-        }
-        if (tid == 0 && iv[5] != 0) {   // .cu:530-566
-            const int size = iv[5], np = iv[6];
-            int r = iv[0] / size > 255 ? 255 : iv[0] / size;
-            int gg = iv[1] / size > 255 ? 255 : iv[1] / size;
-            int b = iv[2] / size > 255 ? 255 : iv[2] / size;
-            r = r < 0 ? 0 : r;
-            gg = gg < 0 ? 0 : gg;
-            b = b < 0 ? 0 : b;
-            int pix_x, pix_y;
-            if (np != 0) {
-                kde_float3 c;
-                c.x = fv[0] / (float)np;
-                c.y = fv[1] / (float)np;
-                c.z = fv[2] / (float)np;
-                centers[cluster_id] = c;
-                const float nx = c.x / c.z, ny = c.y / c.z;
-                pix_x = f2i_rz(nx * intr[0] + intr[2]);
-                pix_y = f2i_rz(intr[5] - ny * intr[4]);
-                if (pix_x < 0 || pix_x >= g.width || pix_y < 0 || pix_y <= g.height) {   // sic, .cu:549
-                    pix_x = iv[3] / size;
-                    pix_y = iv[4] / size;
-                }
-            } else {
-                pix_x = iv[3] / size;
-                pix_y = iv[4] / size;
-            }
-            kde_superpixel m;
-            m.r = (uint8_t)r;
-            m.g = (uint8_t)gg;
-            m.b = (uint8_t)b;
-            m.pad_ = 0;
-            m.x = pix_x;
-            m.y = pix_y;
-            m.size = size;
-            mean[cluster_id] = m;
-        }
-    }
+    kde_superpixel m;
+    m.r = channel_mean(iv[0] / size);
+    m.g = channel_mean(iv[1] / size);
+    m.b = channel_mean(iv[2] / size);
+    m.pad_ = 0;
+    m.x = pix_x;
+    m.y = pix_y;
+    m.size = size;
+    mean[cluster_id] = m;
 }
 
 __global__ __launch_bounds__(256) void analyze_clusters_kernel(DaspGeom g, const uint8_t* __restrict__ bgr,
@@ -507,8 +433,7 @@ __global__ __launch_bounds__(256) void analyze_clusters_kernel(DaspGeom g, const
     const int32_t* __restrict__ labels = sets.s[seg].labels + fpx;
     kde_superpixel* __restrict__ mean = sets.s[seg].mean + fk;
     kde_float3* __restrict__ centers = sets.s[seg].centers + fk;
-    __shared__ int si[7][256];     // r g b x y size npoints
-    __shared__ float sf[3][256];   // X Y Z
+    __shared__ uint32_t buf[10][256];   // the tree's: r g b x y size npoints | X Y Z
     const int tid = threadIdx.x;
     const int tx = tid & 15, ty = tid >> 4;
     const int cluster_id = (int)cid;
@@ -594,7 +519,9 @@ __global__ __launch_bounds__(256) void analyze_clusters_kernel(DaspGeom g, const
         }
       }
     }
-    analyze_reduce_and_store(g, tid, cluster_id, si, sf, r_, g_, b_, x_, y_, s_, n_, xf, yf, zf, mean, centers, intr);
+    int iv[7] = {r_, g_, b_, x_, y_, s_, n_};
+    float fv[3] = {xf, yf, zf};
+    analyze_reduce_and_store(g, tid, cluster_id, buf, iv, fv, mean, centers, intr);
 }
 
 }  // namespace

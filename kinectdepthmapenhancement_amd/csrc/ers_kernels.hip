@@ -11,6 +11,7 @@
 // K10 reads the K9 result and writes a separate buffer (D3).
 #include "kde_internal.h"
 #include "kde_device_math.h"
+#include "kde_device_packed.h"
 #include <type_traits>
 
 namespace kde {
@@ -333,12 +334,6 @@ __global__ __launch_bounds__(256) void edge_fused_kernel(int width, int height,
 // -------------------------------------------------------------------------------------------------
 constexpr int kTileX = 32, kTileY = 8, kThreads = 256;
 
-__device__ __forceinline__ uint32_t load_bgrx(const uint8_t* __restrict__ img, size_t pix)
-{
-    const uint8_t* p = img + pix * 3;
-    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
-}
-
 __device__ __forceinline__ int color_dist2(uint32_t a, uint32_t b)
 {
     int d0 = (int)(a & 0xffu) - (int)(b & 0xffu);
@@ -646,9 +641,6 @@ __global__ __launch_bounds__(kThreads) void enhance7_kernel(const Enh7Dev a)
 // Scales are kept finite (<= 3e38) so that 0 * scale is 0; the reference's 0/0 = NaN case (Q6: flat patch, so
 // adaptive sigma == 0, and a rank whose table sigma has underflowed) is re-created by a rare post-pass.
 // -------------------------------------------------------------------------------------------------
-typedef float e_f2 __attribute__((ext_vector_type(2)));
-typedef uint32_t e_u2 __attribute__((ext_vector_type(2)));
-
 constexpr int kE7BX = 32, kE7BY = 8;        // threads; tile = 64 x 8 pixels
 constexpr float kLabelScale = 32.0f;        // labels are compared as floats at this scale (see the staging loop)
 
@@ -668,27 +660,7 @@ struct Enh7PkDev {
     KDE_STAGE(float* stage_avg; float* stage_dev; unsigned* stage_counters; int stage_force;)   // libkde_hip_stage.so only
 };
 
-__device__ __forceinline__ e_f2 e_fma(e_f2 a, e_f2 b, e_f2 c) { return __builtin_elementwise_fma(a, b, c); }
-__device__ __forceinline__ e_f2 e_bcast(float v) { return e_f2{v, v}; }
-__device__ __forceinline__ e_f2 e_add_clamp(e_f2 a, e_f2 b)
-{
-    e_f2 r;
-    asm("v_pk_add_f32 %0, %1, %2 clamp" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ e_f2 e_mul_clamp(e_f2 a, e_f2 b)
-{
-    e_f2 r;
-    asm("v_pk_mul_f32 %0, %1, %2 clamp" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-// clamp(c - a*b)
-__device__ __forceinline__ e_f2 e_fnma_clamp(e_f2 a, e_f2 b, e_f2 c)
-{
-    e_f2 r;
-    asm("v_pk_fma_f32 %0, %1, %2, %3 neg_lo:[1,0,0] neg_hi:[1,0,0] clamp" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
+// f2 / u2, pk_fma, bcast, the clamp forms and the unit pickers: kde_device_packed.h
 // v_min_f32 without the canonicalising v_max that fminf() puts in front of it (operands are never signalling NaNs)
 __device__ __forceinline__ float min_raw(float x, float y)
 {
@@ -714,7 +686,7 @@ constexpr int kK10Waves = 0;
 template <bool FUSED_LABEL>
 __global__ __launch_bounds__(kE7BX* kE7BY) __attribute__((amdgpu_waves_per_eu(kK10Waves ? kK10Waves : 1))) void enhance7_pk_kernel(const Enh7PkDev a)
 {
-    constexpr int WIN = 7, R = 3, HALF = 3, SEGP = 4;
+    constexpr int WIN = 7, R = 3, SEGP = 4;
     constexpr int NT = kE7BX * kE7BY;
     constexpr int TW = kE7BX * 2, TH = kE7BY;
     constexpr int P = TW + 2 * R, LH = TH + 2 * R;          // P is even: a thread's window starts on an even column
@@ -811,7 +783,7 @@ __global__ __launch_bounds__(kE7BX* kE7BY) __attribute__((amdgpu_waves_per_eu(kK
     const size_t p = (size_t)y * a.width + xb;
 
     uint32_t cc[2];
-    e_f2 negC, cl;
+    f2 negC, cl;
 #pragma unroll
     for (int h = 0; h < 2; h++) {
         cc[h] = s_c[(ty + R) * P + sx + R + h] & 0x00ffffffu;
@@ -821,70 +793,62 @@ __global__ __launch_bounds__(kE7BX* kE7BY) __attribute__((amdgpu_waves_per_eu(kK
     cl.y = has1 ? kLabelScale * (float)in_labels[p + 1] : 2.0e12f;
 
     // unit u of a row: (tap of p0, tap of p1) taken from ONE aligned LDS pair -- straight / swapped / leftover
-    auto pick_u = [&](const e_u2* v, int u, uint32_t& v0, uint32_t& v1) {
-        if (u <= HALF) { v0 = v[u].x; v1 = v[u].y; }
-        else if (u < WIN - 1) { v0 = v[u - HALF].y; v1 = v[u - HALF].x; }
-        else { v0 = v[0].y; v1 = v[HALF].x; }
-    };
-    auto pick_f = [&](const e_f2* v, int u) -> e_f2 {
-        if (u <= HALF) return v[u];
-        if (u < WIN - 1) return __builtin_shufflevector(v[u - HALF], v[u - HALF], 1, 0);
-        return e_f2{v[0].y, v[HALF].x};
-    };
-    auto load_f = [&](const float* plane, int i, e_f2* out) {
+    auto pick_u = [&](const u2* v, int u, uint32_t& v0, uint32_t& v1) { pair_unit_pick(v, WIN, u, 0, v0, v1); };
+    auto pick_f = [&](const f2* v, int u) -> f2 { return pair_unit_pick(v, WIN, u); };
+    auto load_f = [&](const float* plane, int i, f2* out) {
 #pragma unroll
-        for (int m = 0; m < SEGP; m++) out[m] = *reinterpret_cast<const e_f2*>(&plane[(ty + i) * P + sx + 2 * m]);
+        for (int m = 0; m < SEGP; m++) out[m] = *reinterpret_cast<const f2*>(&plane[(ty + i) * P + sx + 2 * m]);
     };
-    auto load_u = [&](const uint32_t* plane, int i, e_u2* out) {
+    auto load_u = [&](const uint32_t* plane, int i, u2* out) {
 #pragma unroll
-        for (int m = 0; m < SEGP; m++) out[m] = *reinterpret_cast<const e_u2*>(&plane[(ty + i) * P + sx + 2 * m]);
+        for (int m = 0; m < SEGP; m++) out[m] = *reinterpret_cast<const u2*>(&plane[(ty + i) * P + sx + 2 * m]);
     };
-    const e_f2 one = e_bcast(1.0f);
-    auto label_mask = [&](const e_f2* lp, int u) -> e_f2 {
-        const e_f2 dl = pick_f(lp, u) - cl;
-        return e_fnma_clamp(dl, dl, one);                    // 1 for the centre's label, 0 otherwise (and for invalid taps)
+    const f2 one = bcast(1.0f);
+    auto label_mask = [&](const f2* lp, int u) -> f2 {
+        const f2 dl = pick_f(lp, u) - cl;
+        return pk_fnma_clamp(dl, dl, one);                    // 1 for the centre's label, 0 otherwise (and for invalid taps)
     };
 
     // -cd (exact) of the two taps of unit u
-    auto unit_ncd = [&](const e_u2* cp, const e_u2* np, int u) -> e_f2 {
+    auto unit_ncd = [&](const u2* cp, const u2* np, int u) -> f2 {
         uint32_t c0, c1, n0, n1;
         pick_u(cp, u, c0, c1);
         pick_u(np, u, n0, n1);
         const uint32_t u0 = (dot4u(c0, cc[0]) << 1) + n0;
         const uint32_t u1 = (dot4u(c1, cc[1]) << 1) + n1;
-        return e_f2{__uint_as_float(u0), __uint_as_float(u1)} + negC;
+        return f2{__uint_as_float(u0), __uint_as_float(u1)} + negC;
     };
 
     // ---- pass 1: label-restricted weighted average (.cu:116-139) --------------------------------------
     // (row loops stay rolled: 100 VGPRs / 4 waves per SIMD; -cd is recomputed in pass 3 rather than cached)
-    e_f2 wsum = e_bcast(0.0f), wgt = e_bcast(0.0f);
-    e_f2 kc1 = e_bcast(a.kc1);
+    f2 wsum = bcast(0.0f), wgt = bcast(0.0f);
+    f2 kc1 = bcast(a.kc1);
     asm volatile("" : "+v"(kc1));          // VGPR pair: the only scalar operand of the argument fma is the log2(S) pair
 #pragma unroll 1
     for (int i = 0; i < WIN; i++) {
-        e_f2 dp[SEGP], lp[SEGP];
-        e_u2 cp[SEGP], np[SEGP];
+        f2 dp[SEGP], lp[SEGP];
+        u2 cp[SEGP], np[SEGP];
         load_f(s_d, i, dp);
         load_f(s_l, i, lp);
         load_u(s_c, i, cp);
         load_u(s_n, i, np);
 #pragma unroll
         for (int u = 0; u < WIN; u++) {
-            const e_f2 nc = unit_ncd(cp, np, u);
-            const e_f2 lsj = *reinterpret_cast<const e_f2*>(&a.lsp[(i * WIN + u) * 2]);
-            const e_f2 a1 = e_fma(nc, kc1, lsj);
+            const f2 nc = unit_ncd(cp, np, u);
+            const f2 lsj = *reinterpret_cast<const f2*>(&a.lsp[(i * WIN + u) * 2]);
+            const f2 a1 = pk_fma(nc, kc1, lsj);
             // same-label test folded into the argument (r04; was f * clamp(1 - dl^2): one packed instruction more per unit):
             // dl == 0 leaves a1 untouched (-0 * 0 + a1), any other label subtracts >= 1024 and v_exp_f32 returns exactly 0 --
             // the same bits as the product with the {0,1} mask
-            e_f2 f;
+            f2 f;
             if constexpr (FUSED_LABEL) {
-                const e_f2 dl = pick_f(lp, u) - cl;
-                const e_f2 a1m = e_fma(-dl, dl, a1);
-                f = e_f2{__builtin_amdgcn_exp2f(a1m.x), __builtin_amdgcn_exp2f(a1m.y)};
+                const f2 dl = pick_f(lp, u) - cl;
+                const f2 a1m = pk_fma(-dl, dl, a1);
+                f = f2{__builtin_amdgcn_exp2f(a1m.x), __builtin_amdgcn_exp2f(a1m.y)};
             } else {
-                f = e_f2{__builtin_amdgcn_exp2f(a1.x), __builtin_amdgcn_exp2f(a1.y)} * label_mask(lp, u);
+                f = f2{__builtin_amdgcn_exp2f(a1.x), __builtin_amdgcn_exp2f(a1.y)} * label_mask(lp, u);
             }
-            wsum = e_fma(pick_f(dp, u), f, wsum);
+            wsum = pk_fma(pick_f(dp, u), f, wsum);
             wgt = wgt + f;
         }
     }
@@ -892,21 +856,21 @@ __global__ __launch_bounds__(kE7BX* kE7BY) __attribute__((amdgpu_waves_per_eu(kK
     // ---- pass 2: mean absolute deviation over the same taps (.cu:143-156) and, from it, the adaptive sigma's scale,
     // integer skip threshold and "is exactly 0" flag (.cu:171).  Runs before pass 3 when the tile could not prove the
     // adaptive sigma small, otherwise only afterwards and only for wavefronts with a candidate for the 0/0 quirk.
-    const e_f2 wavg = e_f2{wsum.x / wgt.x, wsum.y / wgt.y};    // IEEE: the integer skip thresholds below depend on it
-    e_f2 inv_a = e_bcast(3.0e38f), nthr_a = e_bcast(-1.0f);     // values of a provably small adaptive sigma
+    const f2 wavg = f2{wsum.x / wgt.x, wsum.y / wgt.y};    // IEEE: the integer skip thresholds below depend on it
+    f2 inv_a = bcast(3.0e38f), nthr_a = bcast(-1.0f);     // values of a provably small adaptive sigma
     bool flat[2] = {false, false};
     KDE_STAGE(float stage_dev2[2] = {0.0f, 0.0f}; bool stage_dev_done = false;)
     auto adaptive_sigma = [&]() {
-        e_f2 dev = e_bcast(0.0f), cnt = e_bcast(0.0f);
+        f2 dev = bcast(0.0f), cnt = bcast(0.0f);
 #pragma unroll 1
         for (int i = 0; i < WIN; i++) {
-            e_f2 dp[SEGP], lp[SEGP];
+            f2 dp[SEGP], lp[SEGP];
             load_f(s_d, i, dp);
             load_f(s_l, i, lp);
 #pragma unroll
             for (int u = 0; u < WIN; u++) {
-                const e_f2 m = label_mask(lp, u);
-                const e_f2 e = pick_f(dp, u) - wavg;
+                const f2 m = label_mask(lp, u);
+                const f2 e = pick_f(dp, u) - wavg;
                 dev.x = __builtin_fmaf(__builtin_fabsf(e.x), m.x, dev.x);
                 dev.y = __builtin_fmaf(__builtin_fabsf(e.y), m.y, dev.y);
                 cnt = cnt + m;
@@ -947,8 +911,8 @@ __global__ __launch_bounds__(kE7BX* kE7BY) __attribute__((amdgpu_waves_per_eu(kK
     // So as soon as every lane of the wavefront has passed rank kfree on both of its pixels, the remaining ROWS run a
     // loop without any colour arithmetic (12 instead of 28 issue slots per unit; typically rows 1..6 of 7).  Lanes
     // with holes in their first row simply keep the wave in the general loop one row longer.
-    const e_f2 T2 = e_bcast(a.t2_skip), kBig = e_bcast(0x1p100f), sd2 = e_bcast(a.sd);
-    e_f2 num = e_bcast(0.0f), den = e_bcast(0.0f);
+    const f2 T2 = bcast(a.t2_skip), kBig = bcast(0x1p100f), sd2 = bcast(a.sd);
+    f2 num = bcast(0.0f), den = bcast(0.0f);
     uint32_t rank0 = 0, rank1 = 0;           // byte offsets into s_t (8 bytes per rank)
     const char* tbase = reinterpret_cast<const char*>(s_t);
     const float tinv_last = a.tinv[a.kfree > 0 ? a.kfree - 1 : 0];
@@ -959,13 +923,13 @@ __global__ __launch_bounds__(kE7BX* kE7BY) __attribute__((amdgpu_waves_per_eu(kK
 #pragma unroll 1
     for (; row < WIN; row++) {
         const int i = row;
-        e_f2 dp[SEGP], vp[SEGP];
-        e_u2 cp[SEGP], np[SEGP];
+        f2 dp[SEGP], vp[SEGP];
+        u2 cp[SEGP], np[SEGP];
         load_f(s_d, i, dp);
         load_u(s_c, i, cp);
         load_u(s_n, i, np);
 #pragma unroll
-        for (int m = 0; m < SEGP; m++) vp[m] = e_add_clamp(dp[m], dp[m]);
+        for (int m = 0; m < SEGP; m++) vp[m] = pk_add_clamp(dp[m], dp[m]);
         // scan-order ranks of the row's taps: p0 covers columns 0..6 of the segment, p1 columns 1..7
         uint32_t r0[WIN], r1[WIN];
 #pragma unroll
@@ -979,23 +943,21 @@ __global__ __launch_bounds__(kE7BX* kE7BY) __attribute__((amdgpu_waves_per_eu(kK
         }
 #pragma unroll
         for (int u = 0; u < WIN; u++) {
-            const int j0 = u <= HALF ? 2 * u : (u < WIN - 1 ? 2 * (u - HALF) + 1 : 1);
-            const int j1 = u <= HALF ? 2 * u : (u < WIN - 1 ? 2 * (u - HALF) - 1 : WIN - 2);
-            const float2 t0 = *reinterpret_cast<const float2*>(tbase + r0[j0]);
-            const float2 t1 = *reinterpret_cast<const float2*>(tbase + r1[j1]);
-            const e_f2 invl = e_f2{min_raw(inv_a.x, t0.x), min_raw(inv_a.y, t1.x)};
-            const e_f2 thr = e_f2{min_raw(nthr_a.x, t0.y), min_raw(nthr_a.y, t1.y)};
-            const e_f2 nc = unit_ncd(cp, np, u);
-            const e_f2 lsj = *reinterpret_cast<const e_f2*>(&a.lsp[(i * WIN + u) * 2]);
-            const e_f2 mc = e_add_clamp(nc, -thr);                       // 0 <=> -cd <= thr: underflowed colour factor skipped
-            const e_f2 ac = e_fma(nc, mc * invl, lsj);                    // log2(S) - cd * log2(e)/(2 cs_k^2)
-            const e_f2 dq = pick_f(dp, u);
-            const e_f2 t = (dq - wavg) * sd2;
-            const e_f2 md = e_mul_clamp(e_fma(-t, t, T2), kBig);          // 0 <=> underflowed depth factor skipped
-            const e_f2 a2 = e_fma(-(t * md), t, ac);
-            const e_f2 f = e_f2{__builtin_amdgcn_exp2f(a2.x), __builtin_amdgcn_exp2f(a2.y)};
-            num = e_fma(dq, f, num);
-            den = e_fma(pick_f(vp, u), f, den);
+            const float2 t0 = *reinterpret_cast<const float2*>(tbase + r0[pair_unit_tap(WIN, u, 0)]);
+            const float2 t1 = *reinterpret_cast<const float2*>(tbase + r1[pair_unit_tap(WIN, u, 1)]);
+            const f2 invl = f2{min_raw(inv_a.x, t0.x), min_raw(inv_a.y, t1.x)};
+            const f2 thr = f2{min_raw(nthr_a.x, t0.y), min_raw(nthr_a.y, t1.y)};
+            const f2 nc = unit_ncd(cp, np, u);
+            const f2 lsj = *reinterpret_cast<const f2*>(&a.lsp[(i * WIN + u) * 2]);
+            const f2 mc = pk_add_clamp(nc, -thr);                       // 0 <=> -cd <= thr: underflowed colour factor skipped
+            const f2 ac = pk_fma(nc, mc * invl, lsj);                    // log2(S) - cd * log2(e)/(2 cs_k^2)
+            const f2 dq = pick_f(dp, u);
+            const f2 t = (dq - wavg) * sd2;
+            const f2 md = pk_mul_clamp(pk_fma(-t, t, T2), kBig);          // 0 <=> underflowed depth factor skipped
+            const f2 a2 = pk_fma(-(t * md), t, ac);
+            const f2 f = f2{__builtin_amdgcn_exp2f(a2.x), __builtin_amdgcn_exp2f(a2.y)};
+            num = pk_fma(dq, f, num);
+            den = pk_fma(pick_f(vp, u), f, den);
         }
         // every (active) lane past rank kfree on both pixels, with a small adaptive sigma?  then no later tap needs colour
         const bool lane_free = a_small && rank0 >= free_off && rank1 >= free_off;
@@ -1013,25 +975,25 @@ __global__ __launch_bounds__(kE7BX* kE7BY) __attribute__((amdgpu_waves_per_eu(kK
 #pragma unroll 1
         for (; row < WIN; row++) {
             const int i = row;
-            e_f2 dp[SEGP], vp[SEGP];
+            f2 dp[SEGP], vp[SEGP];
             load_f(s_d, i, dp);
 #pragma unroll
-            for (int m = 0; m < SEGP; m++) vp[m] = e_add_clamp(dp[m], dp[m]);
+            for (int m = 0; m < SEGP; m++) vp[m] = pk_add_clamp(dp[m], dp[m]);
 #pragma unroll
             for (int u = 0; u < WIN; u++) {
-                const e_f2 lsj = *reinterpret_cast<const e_f2*>(&a.lsp[(i * WIN + u) * 2]);
-                const e_f2 dq = pick_f(dp, u);
-                const e_f2 t = (dq - wavg) * sd2;
-                e_f2 a2;
+                const f2 lsj = *reinterpret_cast<const f2*>(&a.lsp[(i * WIN + u) * 2]);
+                const f2 dq = pick_f(dp, u);
+                const f2 t = (dq - wavg) * sd2;
+                f2 a2;
                 if constexpr (DRULE) {
-                    const e_f2 md = e_mul_clamp(e_fma(-t, t, T2), kBig);      // 0 <=> underflowed depth factor skipped
-                    a2 = e_fma(-(t * md), t, lsj);
+                    const f2 md = pk_mul_clamp(pk_fma(-t, t, T2), kBig);      // 0 <=> underflowed depth factor skipped
+                    a2 = pk_fma(-(t * md), t, lsj);
                 } else {
-                    a2 = e_fma(-t, t, lsj);       // an invalid tap (d = 0) gets some finite weight here; its vp and d are 0
+                    a2 = pk_fma(-t, t, lsj);       // an invalid tap (d = 0) gets some finite weight here; its vp and d are 0
                 }
-                const e_f2 f = e_f2{__builtin_amdgcn_exp2f(a2.x), __builtin_amdgcn_exp2f(a2.y)};
-                num = e_fma(dq, f, num);
-                den = e_fma(pick_f(vp, u), f, den);
+                const f2 f = f2{__builtin_amdgcn_exp2f(a2.x), __builtin_amdgcn_exp2f(a2.y)};
+                num = pk_fma(dq, f, num);
+                den = pk_fma(pick_f(vp, u), f, den);
             }
         }
     };
@@ -1091,7 +1053,7 @@ __global__ __launch_bounds__(kE7BX* kE7BY) __attribute__((amdgpu_waves_per_eu(kK
     })
     KDE_STAGE(if (a.stage_dev) {
         if (!stage_dev_done) {        // the product path never needed this pixel's deviation: form it for the dump only
-            const e_f2 keep_inv = inv_a, keep_thr = nthr_a;
+            const f2 keep_inv = inv_a, keep_thr = nthr_a;
             const bool keep_flat[2] = {flat[0], flat[1]};
             adaptive_sigma();
             inv_a = keep_inv; nthr_a = keep_thr; flat[0] = keep_flat[0]; flat[1] = keep_flat[1];
@@ -1198,10 +1160,8 @@ static int launch_ers_enhance_one(int width, int height, int n, const float* rd,
         };
         for (int i = 0; i < 7; i++)
             for (int u = 0; u < 7; u++) {   // unit -> (tap of p0, tap of p1): see enhance7_pk_kernel
-                const int j0 = u <= 3 ? 2 * u : (u < 6 ? 2 * (u - 3) + 1 : 1);
-                const int j1 = u <= 3 ? 2 * u : (u < 6 ? 2 * (u - 3) - 1 : 5);
-                d.lsp[(i * 7 + u) * 2] = lg(i, j0);
-                d.lsp[(i * 7 + u) * 2 + 1] = lg(i, j1);
+                d.lsp[(i * 7 + u) * 2] = lg(i, pair_unit_tap(7, u, 0));
+                d.lsp[(i * 7 + u) * 2 + 1] = lg(i, pair_unit_tap(7, u, 1));
             }
         // rank table: c_0 = ColorSigma, c_k = c_{k-1} * 0.3f (EdgeRefinedSuperpixel.cu:172-175 while a <= 0.3 c)
         float c = color_sigma;

@@ -29,6 +29,7 @@
 // keeps each XCD on a contiguous band of tiles so halos are shared in that XCD's L2.
 #include "kde_internal.h"
 #include "kde_device_math.h"
+#include "kde_device_packed.h"
 
 #include <type_traits>
 
@@ -98,11 +99,7 @@ __global__ __launch_bounds__(BX* BY) void jbf_fast_kernel(const FastArgs a)
     __shared__ uint32_t s_n[LH * P];
 
     // ---- workgroup -> (tile, frame): XCD k works on the k-th contiguous eighth of the tile list ----
-    const unsigned nblk = gridDim.x;
-    const unsigned lin = blockIdx.x;
-    const unsigned per = nblk / 8, rem = nblk % 8;
-    const unsigned xcd = lin % 8, slot = lin / 8;
-    const unsigned id = xcd * per + (xcd < rem ? xcd : rem) + slot;   // bijective for any nblk
+    const unsigned id = xcd_band_id(blockIdx.x, gridDim.x);
     const unsigned tiles = (unsigned)a.tiles_x * a.tiles_y;
     const unsigned frame_i = fastdiv24(id, a.div_tiles);
     const unsigned tile = id - frame_i * tiles;
@@ -122,8 +119,7 @@ __global__ __launch_bounds__(BX* BY) void jbf_fast_kernel(const FastArgs a)
         if (gx >= 0 && gx < a.width && gy >= 0 && gy < a.height) {
             const size_t q = (size_t)gy * a.width + gx;
             d = depth[q];
-            const uint8_t* p = guide + q * 3;
-            c = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
+            c = load_bgrx(guide, q);
         }
         const bool valid = d > 50.0f;
         s_d[ly * P + lx] = valid ? d : 0.0f;
@@ -270,24 +266,7 @@ __global__ __launch_bounds__(BX* BY) void jbf_fast_kernel(const FastArgs a)
 //  rules 10.64 + 13.64 instructions per unit became 9.73 + 12.73, EXPERIMENTS.md Part I item 12.)
 // The leftover unit's two biases sit in different pairs: two scalar v_fma_f32 instead of v_pk_mov_b32 + v_pk_fma_f32.
 // ---------------------------------------------------------------------------------------------------
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ f2 pk_fma(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
-__device__ __forceinline__ f2 bcast(float v) { return f2{v, v}; }
-// packed add / multiply with the VOP3P clamp bit: the result is clamped to [0, 1] (NaN -> 0, DX10_CLAMP is on)
-__device__ __forceinline__ f2 pk_add_clamp(f2 a, f2 b)
-{
-    f2 r;
-    asm("v_pk_add_f32 %0, %1, %2 clamp" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ f2 pk_mul_clamp(f2 a, f2 b)
-{
-    f2 r;
-    asm("v_pk_mul_f32 %0, %1, %2 clamp" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
+// f2 / u2, the clamp forms and the unit pickers: kde_device_packed.h
 
 // packed 16-bit minimum / maximum (v_pk_min_u16 / v_pk_max_u16) on the two halves of a dword
 typedef unsigned short us2 __attribute__((ext_vector_type(2)));
@@ -388,7 +367,6 @@ void jbf_pk_kernel(const FastArgs a)
     constexpr int G = (RA + TW + R + 3) / 4;          // 4-pixel groups per staged row (vector loader)
     constexpr int P = VL ? (SH + 4 * G + 1) / 2 * 2 : (TW + 2 * R);   // row pitch in dwords (even; a multiple of 4 when SH == 0)
     constexpr int SEGP = NP + R;                      // aligned pairs in the row segment of a thread
-    constexpr int HALF = (WIN - 1) / 2;
     static_assert(RA >= R && P % 2 == 0 && (!VL || ((RA + S1) % 4 == 0 && TW % 4 == 0 && (SH != 0 || P % 4 == 0))), "tile geometry");
     // BYCODE instances (pk_invalid_by_code): ONE array, the three planes interleaved by rows: staged row ly = depth | colour | h_q,
     // P dwords each, at ly * RP.  All the 64-bit pairs a thread reads in one window row then lie within 3 P dwords (< 2040 bytes) of
@@ -408,11 +386,7 @@ void jbf_pk_kernel(const FastArgs a)
 #define l_c(k) (*(BYCODE ? s_rows + P + (k) : s_c + (k)))
 #define l_n(k) (*(BYCODE ? reinterpret_cast<float*>(s_rows) + 2 * P + (k) : s_n + (k)))
 
-    const unsigned nblk = gridDim.x;
-    const unsigned lin = blockIdx.x;
-    const unsigned per = nblk / 8, rem = nblk % 8;
-    const unsigned xcd = lin % 8, slot = lin / 8;
-    const unsigned id = xcd * per + (xcd < rem ? xcd : rem) + slot;
+    const unsigned id = xcd_band_id(blockIdx.x, gridDim.x);
     const unsigned tiles = (unsigned)a.tiles_x * a.tiles_y;
     const unsigned frame_i = fastdiv24(id, a.div_tiles);
     const unsigned tile = id - frame_i * tiles;
@@ -442,8 +416,7 @@ void jbf_pk_kernel(const FastArgs a)
             if (inside) {
                 const size_t q = (size_t)gy * a.width + gx;
                 d = depth[q];
-                const uint8_t* p = guide + q * 3;
-                c = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
+                c = load_bgrx(guide, q);
             }
             const bool valid = d > 50.0f;
             const int li = ly * RP + lx;
@@ -473,8 +446,7 @@ void jbf_pk_kernel(const FastArgs a)
                 for (int k = 0; k < 4; k++) {
                     if (gx + k >= 0 && gx + k < a.width) {
                         d[k] = depth[q + k];
-                        const uint8_t* p = guide + (q + k) * 3;
-                        c[k] = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
+                        c[k] = load_bgrx(guide, q + k);
                     }
                 }
             }
@@ -639,15 +611,8 @@ void jbf_pk_kernel(const FastArgs a)
     auto unit_arg = [&](auto cs_tag, const u2* cp, const f2* np, int pp, int i, int u) -> f2 {
         constexpr bool CS = decltype(cs_tag)::value;
         uint32_t c0, c1;
-        f2 hq;
-        if (u <= HALF) {                       // straight
-            c0 = cp[pp + u].x; c1 = cp[pp + u].y; hq = np[pp + u];
-        } else if (u < WIN - 1) {              // swapped
-            const int m = pp + (u - HALF);
-            c0 = cp[m].y; c1 = cp[m].x; hq = __builtin_shufflevector(np[m], np[m], 1, 0);
-        } else {                               // leftover
-            c0 = cp[pp].y; c1 = cp[pp + HALF].x; hq = bcast(0.0f);   // (not used: two scalar fmas below)
-        }
+        pair_unit_pick(cp, WIN, u, pp, c0, c1);
+        const f2 hq = pair_unit_pick(np, WIN, u, pp);
         // the dot product's accumulator input adds 2^23's bit pattern: the result IS the float 2^23 + a.b (a.b < 2^18)
         const f2 ab = f2{__uint_as_float(dot4(c0, cc[2 * pp], kMagic)), __uint_as_float(dot4(c1, cc[2 * pp + 1], kMagic))};
         // w = 2 (2^23 + a.b) - (2^24 - 2^18 + |b|^2) = 2 a.b - |b|^2 + 2^18 for both taps in ONE packed fma: an integer in
@@ -659,7 +624,7 @@ void jbf_pk_kernel(const FastArgs a)
             // packed form needs a v_pk_mov_b32 into a pair of its own first (same instruction count, two more live registers:
             // 74 instead of 72 VGPRs at window 11 with one pair per thread).  The empty asm only keeps the vectoriser from
             // re-packing them; it emits no instruction.
-            float w0 = __builtin_fmaf(ab.x, 2.0f, np[pp].y), w1 = __builtin_fmaf(ab.y, 2.0f, np[pp + HALF].x);
+            float w0 = __builtin_fmaf(ab.x, 2.0f, hq.x), w1 = __builtin_fmaf(ab.y, 2.0f, hq.y);
             asm("" : "+v"(w0));
             asm("" : "+v"(w1));
             w = f2{w0, w1};
@@ -680,11 +645,7 @@ void jbf_pk_kernel(const FastArgs a)
         if (CS) return pk_fma(ncd, pk_add_clamp(ncd, Tc) * kc2, lsj);   // Q1: underflowed colour factor skipped
         return pk_fma(ncd, kc2, lsj);
     };
-    auto unit_depth = [&](const f2* dp, int pp, int u) -> f2 {
-        if (u <= HALF) return dp[pp + u];
-        if (u < WIN - 1) return __builtin_shufflevector(dp[pp + (u - HALF)], dp[pp + (u - HALF)], 1, 0);
-        return f2{dp[pp].y, dp[pp + HALF].x};
-    };
+    auto unit_depth = [&](const f2* dp, int pp, int u) -> f2 { return pair_unit_pick(dp, WIN, u, pp); };
 
     auto pass1_row = [&](auto cs_tag, auto keep_tag, int i) {
         constexpr bool VP = decltype(cs_tag)::value || !BYCODE;   // validity pairs: where an invalid tap's weight is not 0 by itself
@@ -941,7 +902,6 @@ bool jbf_fast_supported(const JbfLaunch& l)
 // pair (tap of p0, tap of p1) of unit u at tab[(i*W + u)*2 .. +1] (see jbf_pk_kernel).  out: W*W (scalar) / 2*W*W (packed) floats
 void jbf_fast_fill_table(int W, const float* table_host, bool packed, float* out)
 {
-    const int HALF = (W - 1) / 2;
     auto lg = [&](int i, int j) {
         const float sv = table_host[i * W + j];
         return (float)(((sv == 0.0f) ? 0.0 : std::log2((double)sv)) + kScaleLog2);   // S == 0 -> factor skipped
@@ -953,10 +913,8 @@ void jbf_fast_fill_table(int W, const float* table_host, bool packed, float* out
     }
     for (int i = 0; i < W; i++)
         for (int u = 0; u < W; u++) {   // unit -> (tap of p0, tap of p1)
-            const int j0 = u <= HALF ? 2 * u : (u < W - 1 ? 2 * (u - HALF) + 1 : 1);
-            const int j1 = u <= HALF ? 2 * u : (u < W - 1 ? 2 * (u - HALF) - 1 : W - 2);
-            out[(i * W + u) * 2] = lg(i, j0);
-            out[(i * W + u) * 2 + 1] = lg(i, j1);
+            out[(i * W + u) * 2] = lg(i, pair_unit_tap(W, u, 0));
+            out[(i * W + u) * 2 + 1] = lg(i, pair_unit_tap(W, u, 1));
         }
 }
 

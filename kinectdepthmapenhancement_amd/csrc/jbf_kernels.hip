@@ -7,6 +7,7 @@
 // depth 0 so the inner loops carry no bounds tests.  No MFMA: this is a stencil.
 #include "kde_internal.h"
 #include "kde_device_math.h"
+#include "kde_device_packed.h"
 
 namespace kde {
 namespace {
@@ -14,12 +15,6 @@ namespace {
 constexpr int kTileX = 32;
 constexpr int kTileY = 8;
 constexpr int kThreads = kTileX * kTileY;
-
-__device__ __forceinline__ uint32_t load_bgrx(const uint8_t* __restrict__ img, size_t pix)
-{
-    const uint8_t* p = img + pix * 3;
-    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
-}
 
 __device__ __forceinline__ int color_dist2(uint32_t a, uint32_t b)
 {
@@ -164,7 +159,6 @@ __device__ __forceinline__ uint32_t cvt_pk_u8(float v, uint32_t byte, uint32_t o
     asm("v_cvt_pk_u8_f32 %0, %1, %2, %3" : "=v"(r) : "v"(v), "v"(byte), "v"(old));
     return r;
 }
-typedef float pre_f2 __attribute__((ext_vector_type(2)));
 constexpr int kPreTH = kPreBY;
 
 // PX = horizontally adjacent pixels per thread: 4 amortises the byte -> float conversions best, 2 halves the
@@ -311,18 +305,18 @@ __global__ __launch_bounds__(kPreBX* kPreBY, (R <= 2 ? kPreRpWaves : 0)) void pr
         // registers through moves or spills: 0.142 ms), re-using the weight of the mutual tap of the pair (0.105-0.111 ms),
         // converting the six output bytes straight into a dword + a halfword (unaligned dword stores: 0.099 vs 0.098 ms)
         uint32_t cc[kPrePX];
-        pre_f2 sbg[kPrePX];
+        f2 sbg[kPrePX];
         float sr[kPrePX], sden[kPrePX];
 #pragma unroll
         for (int k = 0; k < kPrePX; k++) {
             cc[k] = sc[(ty + R) * LP + tx * kPrePX + R + k];
-            sbg[k] = pre_f2{0.0f, 0.0f};
+            sbg[k] = f2{0.0f, 0.0f};
             sr[k] = sden[k] = 0.0f;
         }
 #pragma unroll
         for (int dy = -R; dy <= R; dy++) {
             uint32_t v[(SEG + 3) / 4 * 4];
-            pre_f2 fbg[SEG];
+            f2 fbg[SEG];
             float fr[SEG];
             if (PX == 4) {
 #pragma unroll
@@ -339,7 +333,7 @@ __global__ __launch_bounds__(kPreBX* kPreBY, (R <= 2 ? kPreRpWaves : 0)) void pr
             }
 #pragma unroll
             for (int q = 0; q < SEG; q++) {
-                fbg[q] = pre_f2{(float)(v[q] & 0xffu), (float)((v[q] >> 8) & 0xffu)};
+                fbg[q] = f2{(float)(v[q] & 0xffu), (float)((v[q] >> 8) & 0xffu)};
                 fr[q] = (float)((v[q] >> 16) & 0xffu);
             }
 #pragma unroll
@@ -356,7 +350,7 @@ __global__ __launch_bounds__(kPreBX* kPreBY, (R <= 2 ? kPreRpWaves : 0)) void pr
                         const uint32_t n1 = __builtin_amdgcn_sad_u8(v[q], cc[k], 0u);   // |db| + |dg| + |dr|
                         w = lut[space2 * 766 + n1];
                     }
-                    sbg[k] = __builtin_elementwise_fma(pre_f2{w, w}, fbg[q], sbg[k]);
+                    sbg[k] = __builtin_elementwise_fma(f2{w, w}, fbg[q], sbg[k]);
                     sr[k] = __builtin_fmaf(w, fr[q], sr[k]);
                     sden[k] += w;
                 }
@@ -370,9 +364,9 @@ __global__ __launch_bounds__(kPreBX* kPreBY, (R <= 2 ? kPreRpWaves : 0)) void pr
         for (int k = 0; k < kPrePX; k++) {
             const float den = sden[k];
             const float r = __builtin_amdgcn_rcpf(den);
-            const pre_f2 qbg = sbg[k] * pre_f2{r, r};
+            const f2 qbg = sbg[k] * f2{r, r};
             float q[3] = {qbg.x, qbg.y, sr[k] * r};
-            const pre_f2 ebg = pre_f2{__builtin_amdgcn_fractf(q[0]), __builtin_amdgcn_fractf(q[1])} - pre_f2{0.5f, 0.5f};
+            const f2 ebg = f2{__builtin_amdgcn_fractf(q[0]), __builtin_amdgcn_fractf(q[1])} - f2{0.5f, 0.5f};
             const float er = __builtin_amdgcn_fractf(q[2]) - 0.5f;
             // distance of the nearest channel to its rounding boundary (one v_min3_f32 with |.| modifiers); a weight sum
             // that is not a positive normal number (NaN / infinite table entries from degenerate sigmas) -> exact path
@@ -693,49 +687,41 @@ __global__ __launch_bounds__(kMrfBX* kMrfBY) void mrf_fast_kernel(MrfFastDev a)
     const int tx = tid % kMrfBX, ty = tid / kMrfBX;
     const int xb = x0 + tx * kMrfPX, y = y0 + ty;
     if (xb >= a.width || y >= a.height) return;
-    // the pair of pixels of this thread in packed math (unit geometry of jbf_fast.hip: straight / swapped / leftover
+    // the pair of pixels of this thread in packed math (unit geometry of kde_device_packed.h: straight / swapped / leftover
     // taps out of aligned LDS pairs; LW and the thread's first column are even)
     static_assert(kMrfPX == 2 && LW % 2 == 0, "pair geometry");
-    constexpr int HALF = (WIN - 1) / 2, SEGP = 1 + R;
+    constexpr int SEGP = 1 + R;
     uint32_t cc[2];
-    pre_f2 negC, num = {0.0f, 0.0f}, den = {0.0f, 0.0f};
+    f2 negC, num = {0.0f, 0.0f}, den = {0.0f, 0.0f};
 #pragma unroll
     for (int k = 0; k < 2; k++) {
         cc[k] = s_c[(ty + R) * LW + tx * 2 + R + k];
         negC[k] = -(kBiasM + (float)__builtin_amdgcn_udot4(cc[k], cc[k], 0u, false));
     }
-    const pre_f2 kc2 = {a.kc, a.kc}, lsm2 = {a.lsm, a.lsm};
+    const f2 kc2 = {a.kc, a.kc}, lsm2 = {a.lsm, a.lsm};
 #pragma unroll
     for (int i = 0; i < WIN; i++) {
-        pre_f2 dp[SEGP];
+        f2 dp[SEGP];
         uint2 cp[SEGP], np[SEGP];
 #pragma unroll
         for (int m = 0; m < SEGP; m++) {
             const int li = (ty + i) * LW + tx * 2 + 2 * m;
-            dp[m] = *reinterpret_cast<const pre_f2*>(&s_d[li]);
+            dp[m] = *reinterpret_cast<const f2*>(&s_d[li]);
             cp[m] = *reinterpret_cast<const uint2*>(&s_c[li]);
             np[m] = *reinterpret_cast<const uint2*>(&s_n[li]);
         }
 #pragma unroll
         for (int u = 0; u < WIN; u++) {
             uint32_t c0, c1, n0, n1;
-            pre_f2 dq;
-            if (u <= HALF) {
-                c0 = cp[u].x; c1 = cp[u].y; n0 = np[u].x; n1 = np[u].y; dq = dp[u];
-            } else if (u < WIN - 1) {
-                const int m = u - HALF;
-                c0 = cp[m].y; c1 = cp[m].x; n0 = np[m].y; n1 = np[m].x;
-                dq = __builtin_shufflevector(dp[m], dp[m], 1, 0);
-            } else {
-                c0 = cp[0].y; c1 = cp[HALF].x; n0 = np[0].y; n1 = np[HALF].x;
-                dq = pre_f2{dp[0].y, dp[HALF].x};
-            }
+            pair_unit_pick(cp, WIN, u, 0, c0, c1);
+            pair_unit_pick(np, WIN, u, 0, n0, n1);
+            const f2 dq = pair_unit_pick(dp, WIN, u);
             // bits of the float 2^23 + 2^18 + 2 a.b - |b|^2; adding negC gives -cd exactly (-1.7e38 if invalid)
             const uint32_t u0 = (__builtin_amdgcn_udot4(c0, cc[0], 0u, false) << 1) + n0;
             const uint32_t u1 = (__builtin_amdgcn_udot4(c1, cc[1], 0u, false) << 1) + n1;
-            const pre_f2 ncd = pre_f2{__uint_as_float(u0), __uint_as_float(u1)} + negC;
-            const pre_f2 arg = __builtin_elementwise_fma(ncd, kc2, lsm2);
-            const pre_f2 f = {__builtin_amdgcn_exp2f(arg.x), __builtin_amdgcn_exp2f(arg.y)};
+            const f2 ncd = f2{__uint_as_float(u0), __uint_as_float(u1)} + negC;
+            const f2 arg = __builtin_elementwise_fma(ncd, kc2, lsm2);
+            const f2 f = {__builtin_amdgcn_exp2f(arg.x), __builtin_amdgcn_exp2f(arg.y)};
             num = __builtin_elementwise_fma(dq, f, num);
             den = den + f;
         }

@@ -19,34 +19,12 @@
 //      comparison of its argument with a host-derived threshold (NA3).
 #include "kde_internal.h"
 #include "kde_device_math.h"
+#include "kde_superpixel_device.h"
 
 namespace kde {
 namespace {
 
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
-#error "nasp_kernels.hip: the SGPR-pair conditions below assume gfx950 (wave64); build with --offload-arch=gfx950"
-#endif
-// conditions kept in an SGPR pair and selected with the VOP3 form: see dasp_kernels.hip (two adjacent VOP2 v_cndmask stall)
-__device__ __forceinline__ uint64_t lt_mask(float x, float y)
-{
-    uint64_t m;
-    asm("v_cmp_lt_f32_e64 %0, %1, %2" : "=s"(m) : "v"(x), "v"(y));
-    return m;
-}
-__device__ __forceinline__ float sel_f(uint64_t m, float a, float b)       // m ? a : b
-{
-    float r;
-    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(b), "v"(a), "s"(m));
-    return r;
-}
-__device__ __forceinline__ int sel_i(uint64_t m, int a, int b)
-{
-    int r;
-    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(b), "v"(a), "s"(m));
-    return r;
-}
-
-__device__ __forceinline__ int f2i_rz(float v) { return (int)v; }   // v_cvt_i32_f32: RZ, saturating, NaN -> 0
+// (lt_mask / sel_f / sel_i, f2i_rz, tree256 and the record tail: kde_superpixel_device.h)
 __device__ __forceinline__ bool ok3_and(const kde_float3& n) { return n.x != -1.0f && n.y != -1.0f && n.z != -1.0f; }   // .cu:57-62
 __device__ __forceinline__ bool ok3_or(const kde_float3& n) { return n.x != -1.0f || n.y != -1.0f || n.z != -1.0f; }    // .cu:240-245
 
@@ -262,41 +240,6 @@ __global__ __launch_bounds__(256) void nasp_calc_ld_kernel(NaspLaunch a)
     f.labels[p] = o.l;
 }
 
-// ---- the 256-way tree of the two cluster kernels (.cu:457-621, :825-999) --------------------------------------------
-// levels +128, +64 through LDS, +32 ... +1 inside the first wavefront; lane 0 of it sees the clean tree.
-// Integer sums wrap as the reference's 32-bit adds do.  buf: (NI + NF) x 256 words of LDS, integer rows first.
-template <int NI, int NF>
-__device__ __forceinline__ void tree256(int tid, uint32_t (*buf)[256], int* iv, float* fv)
-{
-    int(*si)[256] = reinterpret_cast<int(*)[256]>(buf);
-    float(*sf)[256] = reinterpret_cast<float(*)[256]>(buf + NI);
-#pragma unroll
-    for (int k = 0; k < NI; k++) si[k][tid] = iv[k];
-#pragma unroll
-    for (int k = 0; k < NF; k++) sf[k][tid] = fv[k];
-    __syncthreads();
-    if (tid < 128) {
-#pragma unroll
-        for (int k = 0; k < NI; k++) si[k][tid] = (int)((unsigned)si[k][tid] + (unsigned)si[k][tid + 128]);
-#pragma unroll
-        for (int k = 0; k < NF; k++) sf[k][tid] += sf[k][tid + 128];
-    }
-    __syncthreads();
-    if (tid < 64) {
-#pragma unroll
-        for (int k = 0; k < NI; k++) iv[k] = (int)((unsigned)si[k][tid] + (unsigned)si[k][tid + 64]);
-#pragma unroll
-        for (int k = 0; k < NF; k++) fv[k] = sf[k][tid] + sf[k][tid + 64];
-#pragma unroll
-        for (int step = 32; step >= 1; step >>= 1) {
-#pragma unroll
-            for (int k = 0; k < NI; k++) iv[k] = (int)((unsigned)iv[k] + (unsigned)__shfl_down(iv[k], step, 64));
-#pragma unroll
-            for (int k = 0; k < NF; k++) fv[k] += __shfl_down(fv[k], step, 64);
-        }
-    }
-}
-
 // z of the point under a new cluster centre (.cu:635, :1014).  The reference indexes unchecked; a position outside the
 // image (only an overflowing sum or a non-finite weight can produce one) reads z = 0
 __device__ __forceinline__ bool center_point(const DaspGeom& g, const kde_float3* pts, int px, int py, kde_float3* out)
@@ -391,39 +334,26 @@ __device__ __forceinline__ void analyze_pass(const NaspLaunch& a, const FramePtr
         return;
     }
     const int size = iv[5], np = iv[6];
-    int r = iv[0] / size > 255 ? 255 : iv[0] / size;
-    int gg = iv[1] / size > 255 ? 255 : iv[1] / size;
-    int b = iv[2] / size > 255 ? 255 : iv[2] / size;
-    r = r < 0 ? 0 : r;
-    gg = gg < 0 ? 0 : gg;
-    b = b < 0 ? 0 : b;
-    int pix_x = iv[3] / size, pix_y = iv[4] / size;
+    const int mean_x = iv[3] / size, mean_y = iv[4] / size;
+    int pix_x = mean_x, pix_y = mean_y;
     if (np != 0) {
         kde_float3 c;
         if (center_point(g, f.pts, pix_x, pix_y, &c)) {
             f.centers[cluster_id] = c;
         } else {
-            c.x = fv[0] / (float)np;
-            c.y = fv[1] / (float)np;
-            c.z = fv[2] / (float)np;
+            c = mean3(fv[0], fv[1], fv[2], np);
             f.centers[cluster_id] = c;
-            const float nx = c.x / c.z, ny = c.y / c.z;
-            pix_x = f2i_rz(nx * a.intr[0] + a.intr[2]);
-            pix_y = f2i_rz(a.intr[5] - ny * a.intr[4]);
-            if (pix_x < 0 || pix_x >= g.width || pix_y < 0 || pix_y <= g.height) {   // sic, .cu:652
-                pix_x = iv[3] / size;
-                pix_y = iv[4] / size;
-            }
+            reproject_centre(c, a.intr, g.width, g.height, mean_x, mean_y, pix_x, pix_y);   // sic, .cu:652
         }
-        rec->spn = kde_float3{fv[3] / (float)np, fv[4] / (float)np, fv[5] / (float)np};
+        rec->spn = mean3(fv[3], fv[4], fv[5], np);
     } else {
         rec->spn = kde_float3{-1.0f, -1.0f, -1.0f};
         f.centers[cluster_id] = kde_float3{0.0f, 0.0f, 0.0f};
     }
     f.spn[cluster_id] = rec->spn;
-    rec->m.r = (uint8_t)r;
-    rec->m.g = (uint8_t)gg;
-    rec->m.b = (uint8_t)b;
+    rec->m.r = channel_mean(iv[0] / size);
+    rec->m.g = channel_mean(iv[1] / size);
+    rec->m.b = channel_mean(iv[2] / size);
     rec->m.pad_ = 0;
     rec->m.x = pix_x;
     rec->m.y = pix_y;
@@ -487,31 +417,18 @@ __device__ __forceinline__ void weighted_pass(const NaspLaunch& a, const FramePt
     const float size = fv[5];
     if (tid != 0 || !(size != 0.0f)) return;       // .cu:1001-1002 (a NaN sum is != 0)
     const int np = iv[0];
-    int r = f2i_rz(fv[0] / size) > 255 ? 255 : f2i_rz(fv[0] / size);
-    int gg = f2i_rz(fv[1] / size) > 255 ? 255 : f2i_rz(fv[1] / size);
-    int b = f2i_rz(fv[2] / size) > 255 ? 255 : f2i_rz(fv[2] / size);
-    r = r < 0 ? 0 : r;
-    gg = gg < 0 ? 0 : gg;
-    b = b < 0 ? 0 : b;
-    int pix_x = f2i_rz(fv[3] / size), pix_y = f2i_rz(fv[4] / size);
+    const int mean_x = f2i_rz(fv[3] / size), mean_y = f2i_rz(fv[4] / size);
+    int pix_x = mean_x, pix_y = mean_y;
     if (np != 0) {
         kde_float3 c;
         if (center_point(g, f.pts, pix_x, pix_y, &c)) {
             f.centers[cluster_id] = c;
         } else {
-            c.x = fv[6] / (float)np;
-            c.y = fv[7] / (float)np;
-            c.z = fv[8] / (float)np;
+            c = mean3(fv[6], fv[7], fv[8], np);
             f.centers[cluster_id] = c;
-            const float nx = c.x / c.z, ny = c.y / c.z;
-            pix_x = f2i_rz(nx * a.intr[0] + a.intr[2]);
-            pix_y = f2i_rz(a.intr[5] - ny * a.intr[4]);
-            if (pix_x < 0 || pix_x >= g.width || pix_y < 0 || pix_y <= g.height) {   // sic, .cu:1031
-                pix_x = f2i_rz(fv[3] / size);
-                pix_y = f2i_rz(fv[4] / size);
-            }
+            reproject_centre(c, a.intr, g.width, g.height, mean_x, mean_y, pix_x, pix_y);   // sic, .cu:1031
         }
-        kde_float3 n{fv[9] / (float)np, fv[10] / (float)np, fv[11] / (float)np};
+        kde_float3 n = mean3(fv[9], fv[10], fv[11], np);
         const float len = sqrtf(n.x * n.x + n.y * n.y + n.z * n.z);
         n.x /= len;
         n.y /= len;
@@ -524,9 +441,9 @@ __device__ __forceinline__ void weighted_pass(const NaspLaunch& a, const FramePt
         f.variance[cluster_id] = 0.0f;
     }
     kde_superpixel m;
-    m.r = (uint8_t)r;
-    m.g = (uint8_t)gg;
-    m.b = (uint8_t)b;
+    m.r = channel_mean(f2i_rz(fv[0] / size));
+    m.g = channel_mean(f2i_rz(fv[1] / size));
+    m.b = channel_mean(f2i_rz(fv[2] / size));
     m.pad_ = 0;
     m.x = pix_x;
     m.y = pix_y;

@@ -11,6 +11,7 @@
 // to ~1e-15 relative before the cast to float.
 #include "kde_internal.h"
 #include "kde_device_math.h"
+#include "kde_device_packed.h"
 
 namespace kde {
 namespace {
@@ -231,15 +232,8 @@ __global__ __launch_bounds__(kThreads) void set_pseudo_depth_kernel(int npix, in
 // from the input cloud, exactly what 20 in-place float3 sweeps leave behind.
 // (Fusing several sweeps per launch through LDS with a halo was measured slower: the sweep is VALU-bound, and the
 // halo recomputation costs more than the saved traffic.  What pays is packed math: a thread owns two horizontally
-// adjacent pixels and every float op of the 25 taps is a v_pk_*_f32 on the pair -- see jbf_fast.hip for the unit
+// adjacent pixels and every float op of the 25 taps is a v_pk_*_f32 on the pair -- see kde_device_packed.h for the unit
 // geometry -- with the "tap is valid" select folded into a {0, 0.5} factor prepared once per loaded LDS pair.)
-typedef float s_f2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ s_f2 s_add_clamp(s_f2 a, s_f2 b)
-{
-    s_f2 r;
-    asm("v_pk_add_f32 %0, %1, %2 clamp" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
 
 constexpr int kSwBX = 32, kSwBY = 8;                  // threads; tile = 64 x 8 pixels
 __global__ __launch_bounds__(kSwBX* kSwBY) void mrf_sweep_kernel(int width, int height, const float* __restrict__ zin,
@@ -263,7 +257,7 @@ __global__ __launch_bounds__(kSwBX* kSwBY) void mrf_sweep_kernel(int width, int 
     const size_t p = (size_t)y * width + x;
     // this thread's own pixels first: their loads are in flight while the tile is staged (one round trip, not two)
     const float zs0 = own ? zin[p] : 0.0f, zs1 = has1 ? zin[p + 1] : 0.0f;
-    const s_f2 pf = {own ? pfz[p] : 0.0f, has1 ? pfz[p + 1] : 0.0f};
+    const f2 pf = {own ? pfz[p] : 0.0f, has1 ? pfz[p + 1] : 0.0f};
     for (int i = threadIdx.x; i < LW * LH; i += kSwBX * kSwBY) {
         const int ly = i / LW, lx = i - ly * LW;
         const int gx = x0 + lx - R, gy = y0 + ly - R;
@@ -273,25 +267,27 @@ __global__ __launch_bounds__(kSwBX* kSwBY) void mrf_sweep_kernel(int width, int 
     }
     __syncthreads();
     if (!own) return;
-    s_f2 oz = {fabsf(zs0), fabsf(zs1)};
+    f2 oz = {fabsf(zs0), fabsf(zs1)};
     bool rw0 = zs0 < 0.0f, rw1 = zs1 < 0.0f;
     const bool c0 = pf.x > 50.0f && fabsf(oz.x - pf.x) < oz.x * 0.01f;
     const bool c1 = pf.y > 50.0f && fabsf(oz.y - pf.y) < oz.y * 0.01f;
     if (c0 || c1) {
-        s_f2 num = pf, den = {1.0f, 1.0f};
-        const s_f2 one = {1.0f, 1.0f}, half = {0.5f, 0.5f};
+        f2 num = pf, den = {1.0f, 1.0f};
+        const f2 one = {1.0f, 1.0f}, half = {0.5f, 0.5f};
 #pragma unroll
         for (int i = 0; i < WIN; i++) {
-            s_f2 q[3], hv[3];
+            f2 q[3], hv[3];
 #pragma unroll
             for (int m = 0; m < 3; m++) {
-                q[m] = *reinterpret_cast<const s_f2*>(&sz[(ty + i) * LW + 2 * tx + 2 * m]);
-                hv[m] = s_add_clamp(q[m], q[m]) * half;             // 0.5 for a valid tap (z > 50), 0 otherwise
+                q[m] = *reinterpret_cast<const f2*>(&sz[(ty + i) * LW + 2 * tx + 2 * m]);
+                hv[m] = pk_add_clamp(q[m], q[m]) * half;             // 0.5 for a valid tap (z > 50), 0 otherwise
             }
 #pragma unroll
             for (int u = 0; u < WIN; u++) {
                 // unit u = (tap of p0, tap of p1) out of ONE aligned pair: straight / swapped / leftover
-                s_f2 oq, h;
+                // (written out, not pair_unit_pick: two picks instead of this one branch commute the operands of the
+                //  packed multiplies below, and the kernel's code is held to the instruction)
+                f2 oq, h;
                 if (u <= HALF) {
                     oq = q[u];
                     h = hv[u];
@@ -299,13 +295,13 @@ __global__ __launch_bounds__(kSwBX* kSwBY) void mrf_sweep_kernel(int width, int 
                     oq = __builtin_shufflevector(q[u - HALF], q[u - HALF], 1, 0);
                     h = __builtin_shufflevector(hv[u - HALF], hv[u - HALF], 1, 0);
                 } else {
-                    oq = s_f2{q[0].y, q[HALF].x};
-                    h = s_f2{hv[0].y, hv[HALF].x};
+                    oq = f2{q[0].y, q[HALF].x};
+                    h = f2{hv[0].y, hv[HALF].x};
                 }
-                const s_f2 diff = oz - oq;
-                const s_f2 t1 = one + diff * diff;
+                const f2 diff = oz - oq;
+                const f2 t1 = one + diff * diff;
                 // K / (1 + diff^2) * smooth_sigma with K = 0.5, smooth_sigma = 1; v_rcp_f32 (1 ulp) for the division
-                const s_f2 filter = s_f2{__builtin_amdgcn_rcpf(t1.x), __builtin_amdgcn_rcpf(t1.y)} * h;
+                const f2 filter = f2{__builtin_amdgcn_rcpf(t1.x), __builtin_amdgcn_rcpf(t1.y)} * h;
                 num = __builtin_elementwise_fma(oq, filter, num);
                 den = den + filter;
             }

@@ -10,6 +10,7 @@
 // reproduced (every output element is overwritten).
 #include "kde_internal.h"
 #include "kde_device_math.h"
+#include "kde_device_packed.h"
 
 namespace kde {
 namespace {
@@ -263,15 +264,14 @@ __global__ __launch_bounds__(kThreads) void buf_get_kernel(const kde_weighted_d*
 // Four records (32 B) per thread, depth frames read as float4, two frames in flight.  The rule is evaluated
 // branch-free on pairs of records: the float arithmetic is the reference's own operations in its own order
 // (v_pk_mul / v_pk_add / IEEE division; rw*2+1 as one fma is exact because rw*2 is), selected at the end.
-typedef float s_f2 __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ void update_pair(s_f2& rd, s_f2& rw, s_f2 d)
+__device__ __forceinline__ void update_pair(f2& rd, f2& rw, f2 d)
 {
-    const s_f2 one = {1.0f, 1.0f};
-    const s_f2 rw1 = rw + one;
-    const s_f2 sum = (rd * rw1) + (d * rw);                                     // ((ref.d*(w+1)) + (d*w))
-    const s_f2 den = __builtin_elementwise_fma(rw, s_f2{2.0f, 2.0f}, one);     // (w*2+1), exact as an fma
-    const s_f2 lim = d * s_f2{0.01f, 0.01f};
+    const f2 one = {1.0f, 1.0f};
+    const f2 rw1 = rw + one;
+    const f2 sum = (rd * rw1) + (d * rw);                                 // ((ref.d*(w+1)) + (d*w))
+    const f2 den = __builtin_elementwise_fma(rw, f2{2.0f, 2.0f}, one);    // (w*2+1), exact as an fma
+    const f2 lim = d * f2{0.01f, 0.01f};
 #pragma unroll
     for (int k = 0; k < 2; k++) {
         const float q = sum[k] / den[k];
@@ -295,14 +295,14 @@ __global__ __launch_bounds__(kThreads) void buf_update4_kernel(kde_weighted_d* _
     for (size_t g = (size_t)blockIdx.x * kThreads + threadIdx.x; g < quads; g += stride) {
         float4* bp = reinterpret_cast<float4*>(buf) + 2 * g;
         const float4 r0 = bp[0], r1 = bp[1];
-        s_f2 rdA = {r0.x, r0.z}, rwA = {r0.y, r0.w}, rdB = {r1.x, r1.z}, rwB = {r1.y, r1.w};
+        f2 rdA = {r0.x, r0.z}, rwA = {r0.y, r0.w}, rdB = {r1.x, r1.z}, rwB = {r1.y, r1.w};
         const float4* dp = reinterpret_cast<const float4*>(d) + g;
         const size_t fstride = n / 4;                      // frames are n floats apart (n % 4 == 0 on this path)
         float4 cur = ld4(dp, NT);
         for (int f = 0; f < n_frames; f++) {
             const float4 nxt = f + 1 < n_frames ? ld4(dp + (size_t)(f + 1) * fstride, NT) : cur;
-            update_pair(rdA, rwA, s_f2{cur.x, cur.y});
-            update_pair(rdB, rwB, s_f2{cur.z, cur.w});
+            update_pair(rdA, rwA, f2{cur.x, cur.y});
+            update_pair(rdB, rwB, f2{cur.z, cur.w});
             cur = nxt;
         }
         bp[0] = make_float4(rdA.x, rwA.x, rdA.y, rwA.y);

@@ -595,6 +595,48 @@ def test_fastdiv24_device_function_equals_integer_division(torch_cuda):
         assert np.array_equal(got, big // np.uint32(d)), (d, maxdiv)
 
 
+def _tree256_order(row):
+    """The cluster kernels' 256-way tree on one row, in the row's own arithmetic: levels +128 and +64, then +32 ... +1 with
+    __shfl_down semantics inside the 64 remaining lanes (a lane whose partner lies beyond lane 63 adds its own value);
+    lane 0 holds the result."""
+    a = row[:128] + row[128:]
+    b = a[:64] + a[64:]
+    for step in (32, 16, 8, 4, 2, 1):
+        b = b + np.concatenate([b[step:], b[64 - step:]])
+    return b[0]
+
+
+def test_cluster_tree256_keeps_the_reference_summation_order(torch_cuda):
+    """csrc/kde_superpixel_device.h tree256, the reduction both superpixel segmenters run, through tools/hooks: float sums
+    to the bit on inputs whose sum depends on the order of additions, integer sums modulo 2^32 on inputs that wrap."""
+    import importlib.util
+    import math
+    import os
+    from conftest import ROOT
+    spec = importlib.util.spec_from_file_location("kde_hooks", os.path.join(ROOT, "tools", "hooks", "hooks.py"))
+    hooks = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(hooks)
+    t = torch_cuda
+    rng = np.random.default_rng(256)
+    fv = np.empty((2, 256), np.float32)
+    fv[0] = (np.exp2(rng.uniform(0.0, 30.0, 256)) * rng.choice([-1.0, 1.0], 256)).astype(np.float32)
+    fv[1] = np.resize(np.array([1e8, 1.0, -1e8], np.float32), 256)
+    iv = np.empty((2, 256), np.uint32)
+    iv[0] = 0x01000001                                   # 256 of them: 2^32 + 256
+    iv[1] = (1 << 24) + np.arange(256, dtype=np.uint32)  # the running sum passes INT_MAX half way, the total passes 2^32
+    want_f = np.array([_tree256_order(fv[0]), _tree256_order(fv[1])], np.float32)
+    for r in range(2):      # the order matters on these rows: the left-to-right sum or the exact sum is another float
+        serial = np.float32(0.0)
+        for v in fv[r]:
+            serial = np.float32(serial + v)
+        assert len({float(want_f[r]), float(serial), float(np.float32(math.fsum(fv[r].tolist())))}) > 1
+    want_i = [int(_tree256_order(iv[r].astype(np.uint64))) & 0xFFFFFFFF for r in range(2)]
+    assert want_i == [sum(map(int, iv[r])) % (1 << 32) for r in range(2)] and want_i[0] == 256
+    got = hooks.tree256(t.from_numpy(iv.view(np.int32)).cuda(), t.from_numpy(fv).cuda(), t.cuda.current_stream().cuda_stream)
+    assert [int(got[0]), int(got[1])] == want_i
+    assert np.array_equal(got[2:], want_f.view(np.uint32)), (got[2:], want_f.view(np.uint32))
+
+
 def test_spdsr_object_reuse_starts_from_clean_moment_tables(torch_cuda, F, oracle, synth):
     """The per-cluster moment tables are accumulated with atomics into zeroed memory and cleared by the kernel that consumes
     them (no memset launches per frame): a second, different frame — and a smaller batch after a larger one — on the SAME

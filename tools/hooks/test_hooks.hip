@@ -6,6 +6,7 @@
 
 #include "../../include/kde_test_hooks.h"
 #include "../../kinectdepthmapenhancement_amd/csrc/kde_device_math.h"
+#include "../../kinectdepthmapenhancement_amd/csrc/kde_superpixel_device.h"
 
 namespace {
 
@@ -50,7 +51,31 @@ __global__ __launch_bounds__(256) void bgr3_copy_kernel(const uint8_t* __restric
     oh[2] = (uint16_t)(b >> 8);
 }
 
+// one workgroup: thread t contributes element t of every row; lane 0's tree256<2, 2> results, integers first
+__global__ __launch_bounds__(256) void tree256_probe_kernel(const int32_t* __restrict__ iv_rows, const float* __restrict__ fv_rows,
+                                                           uint32_t* __restrict__ out)
+{
+    __shared__ uint32_t buf[4][256];
+    const int tid = threadIdx.x;
+    int iv[2] = {iv_rows[tid], iv_rows[256 + tid]};
+    float fv[2] = {fv_rows[tid], fv_rows[256 + tid]};
+    kde::tree256<2, 2>(tid, buf, iv, fv);
+    if (tid == 0) {
+        out[0] = (uint32_t)iv[0];
+        out[1] = (uint32_t)iv[1];
+        out[2] = __float_as_uint(fv[0]);
+        out[3] = __float_as_uint(fv[1]);
+    }
+}
+
 }  // namespace
+
+extern "C" int kde_test_tree256(const int32_t* iv_rows_dev, const float* fv_rows_dev, uint32_t* out_dev, void* stream)
+{
+    if (!iv_rows_dev || !fv_rows_dev || !out_dev) return 1;
+    hipLaunchKernelGGL(tree256_probe_kernel, dim3(1), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), iv_rows_dev, fv_rows_dev, out_dev);
+    return hipGetLastError() == hipSuccess ? 0 : 4;
+}
 
 extern "C" int kde_bench_bgr3_copy(const void* src_dev, void* dst_dev, size_t npix, void* stream)
 {
