@@ -18,6 +18,7 @@
 //                                 main.cpp:160-163, 198-202, with the result as a point cloud or a depth map)
 //   kde::MeanError3D              (extension: the quality figure of main.cpp:220-308 for a batch, on the device)
 //   kde::PointCloudXYZRGB         (extension: the coloured clouds of main.cpp:211-300 for a batch, compacted on the device)
+//   kde::DepthRegistration        (extension: what Kinect.cpp:71-75 asks OpenNI for -- depth warped into the colour camera's view)
 //
 // What differs from the reference headers, and why:
 //   * cv::gpu::GpuMat parameters are templates over "anything with .data/.rows/.cols/.step" — a real
@@ -952,6 +953,11 @@ public:
         require_continuous_8uc3(color_device, Width, Height, "KinectDepthEnhancement::Process");
         check(kde_enh_process_batch(h_, 1, depth_device, color_device.data, stream_));
     }
+    // added: n independent frames back to back (kde_enh_process_batch), n at most the max_batch of the constructor
+    void ProcessBatch(int n, const float* depth_device, const uint8_t* bgr_device)
+    {
+        check(kde_enh_process_batch(h_, n, depth_device, bgr_device, stream_));
+    }
     float3* getOptimizedPoints_Device()
     {
         kde_float3* p = nullptr;
@@ -1194,6 +1200,86 @@ public:
 
 private:
     kde_cloud* h_ = nullptr;
+    void* stream_ = nullptr;
+};
+
+// extension (no reference counterpart as a class): the registration Kinect::InitAllData asks OpenNI for (Kinect.cpp:71-75),
+// on the device (kde_reg_*): n depth frames (float* or uint16_t*) warped into the colour camera's view through a z-buffer, so
+// that depth pixel (x, y) and colour pixel (x, y) look along the same ray, as every class above assumes.  The rule is stated
+// in kde_hip.h: the nearest source pixel wins, the result is deterministic to the bit; cx and cy are kept as floats; no lens
+// distortion.  registerDepth() is asynchronous on the object's stream and capturable; the *_Host members synchronise.
+class DepthRegistration {
+public:
+    static kde_reg_params defaultParams()
+    {
+        kde_reg_params p{};
+        check(kde_reg_default_params(&p));
+        return p;
+    }
+    DepthRegistration(int depth_width, int depth_height, int color_width, int color_height, int max_batch = 1)
+    {
+        check(kde_reg_create(&h_, depth_width, depth_height, color_width, color_height, max_batch, nullptr));
+    }
+    DepthRegistration(int depth_width, int depth_height, int color_width, int color_height, int max_batch, const kde_reg_params& params)
+    {
+        check(kde_reg_create(&h_, depth_width, depth_height, color_width, color_height, max_batch, &params));
+    }
+    ~DepthRegistration() { kde_reg_destroy(h_); }
+    DepthRegistration(const DepthRegistration&) = delete;
+    DepthRegistration& operator=(const DepthRegistration&) = delete;
+
+    // the two intrinsic matrices, R (row-major 3 x 3) and t (millimetres): P_colour = R * P_depth + t
+    template <class MatLike>
+    void setCalibration(const MatLike& depth_intrinsic, const MatLike& color_intrinsic, const double* R9, const double* t3)
+    {
+        double kd[9], kc[9];
+        intrinsic_to_array(depth_intrinsic, kd);
+        intrinsic_to_array(color_intrinsic, kc);
+        check(kde_reg_set_calibration(h_, kd, kc, R9, t3));
+    }
+    // n frames back to back; the output format is the type of out_device (nullptr of that type: the object-owned buffer)
+    template <class Depth, class Out>
+    void registerDepth(int n, const Depth* depth_device, Out* out_device)
+    {
+        check(kde_reg_register_batch(h_, n, depth_device, format(depth_device), format(out_device), out_device, stream_));
+    }
+    // the colour image as the depth camera sees it (no occlusion test): bgr_frames = 1 (one image for every frame) or n
+    template <class Depth>
+    void colorToDepth(int n, const Depth* depth_device, const uint8_t* bgr_device, int bgr_frames, uint8_t* out_bgr_device)
+    {
+        check(kde_reg_color_to_depth_batch(h_, n, depth_device, format(depth_device), bgr_device, bgr_frames, out_bgr_device, stream_));
+    }
+    void* depth_Device() const
+    {
+        void* p = nullptr;
+        check(kde_reg_depth_device(h_, &p));
+        return p;
+    }
+    const void* depth_Host() const
+    {
+        const void* p = nullptr;
+        check(kde_reg_depth_host(h_, stream_, &p));
+        return p;
+    }
+    uint32_t* filled_Device() const
+    {
+        uint32_t* p = nullptr;
+        check(kde_reg_filled_device(h_, &p));
+        return p;
+    }
+    const uint32_t* filled_Host() const
+    {
+        const uint32_t* p = nullptr;
+        check(kde_reg_filled_host(h_, stream_, &p));
+        return p;
+    }
+    void setStream(void* hip_stream) { stream_ = hip_stream; }
+    kde_reg* handle() const { return h_; }
+
+private:
+    static int format(const float*) { return KDE_DEPTH_F32; }
+    static int format(const uint16_t*) { return KDE_DEPTH_U16; }
+    kde_reg* h_ = nullptr;
     void* stream_ = nullptr;
 };
 

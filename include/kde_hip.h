@@ -659,6 +659,82 @@ int kde_cloud_counts_host(kde_cloud* h, void* stream, const uint32_t** out);
  * out_dev of the last call must still be alive.  Synchronises. */
 int kde_cloud_points_host(kde_cloud* h, void* stream, const kde_cloud_point** out, const uint64_t** offsets);
 
+/* ==========================================================================================
+ * DepthRegistration: depth warped into the colour camera's view.  Every class of this library assumes that depth pixel
+ * (x, y) and colour pixel (x, y) look along the same ray; the reference gets that from outside its own code:
+ * Kinect::InitAllData (Kinect.cpp:71-75) asks OpenNI to register the depth stream to the image stream before any frame
+ * reaches main.cpp.  Frames from any other source (the host feeds take "the sensor's uint16 depth") are registered here, for
+ * a batch on the device, by a scatter through a z-buffer.
+ *
+ * Calibration: the depth camera (fxd, fyd, cxd, cyd) and the colour camera (fxc, fyc, cxc, cyc), each from a row-major 3 x 3
+ * double matrix converted to float, and P_colour = R * P_depth + t (R 9 doubles row-major, t 3 doubles in millimetres, both
+ * converted to float).  Axes: x right, y down, z forward; pixel centres at integer coordinates.  cx AND cy ARE KEPT AS
+ * FLOATS HERE, not truncated to int as DimensionConvertor does (DimensionConvertor.cpp:3-13): calibrated principal points
+ * are no integers, and truncating two cameras independently would move the result by up to a pixel.  No lens distortion.
+ *
+ * The rule.  Every operation is one IEEE binary32 operation in the order written, no fused multiply-add, divisions
+ * correctly rounded.  For source pixel (u, v) of frame f with depth z (float, or (float)u16):
+ *   valid     iff z > z_min && z < z_max (defaults 0 and FLT_MAX: NaN, +-inf, 0 and negatives are invalid)
+ *   project(a, b):  xn = (a - cxd) / fxd;  yn = (b - cyd) / fyd;  X = xn * z;  Y = yn * z
+ *             Xc = ((r00 * X + r01 * Y) + r02 * z) + tx, Yc and Zc likewise from rows 1 and 2
+ *             fails unless Zc > z_min && Zc < z_max
+ *             uc = fxc * (Xc / Zc) + cxc;  vc = fyc * (Yc / Zc) + cyc
+ *   centre    project((float)u, (float)v); a failed centre drops the pixel.  The value written is the centre's Zc, its key
+ *             the bit pattern of Zc as uint32 (Zc is positive, so unsigned order is numeric order).
+ *   point mode (max_splat == 0): iu = rintf(uc), iv = rintf(vc) (ties to even); kept iff iu >= 0 && iu <= Wc - 1 &&
+ *             iv >= 0 && iv <= Hc - 1, tested on the floats (a NaN fails); zbuf[f][iv][iu] = min(zbuf, key)
+ *   splat mode (max_splat in 1..16), which closes the cracks a one-pixel scatter leaves when the target is finer:
+ *             (ua, va) = project(u - 0.5f, v - 0.5f), (ub, vb) = project(u + 0.5f, v + 0.5f) at the same z; either failing
+ *             or a NaN coordinate drops the pixel.  Columns i0 = max(ceilf(min(ua, ub)), 0) .. i1 = min(ceilf(max(ua, ub))
+ *             - 1, Wc - 1): the integers of a half-open interval, so abutting footprints tile the line; a span longer than
+ *             max_splat is cut to i0 .. i0 + max_splat - 1; rows likewise; an empty span writes nothing.  Every covered
+ *             target pixel takes the min with the centre's key.
+ *   finalise  a target pixel no source pixel reached is 0 (the sensor's "invalid"); any other is Zc unchanged
+ *             (KDE_DEPTH_F32) or depth_to_u16(Zc) as kde_points_to_depth rounds (KDE_DEPTH_U16).  filled[f] = the number of
+ *             target pixels reached, counted on the keys, not on the rounded uint16.
+ * The min of keys does not depend on arrival order and the count is an integer sum: the result is deterministic to the bit
+ * and does not depend on n, a frame's position in the batch or pointer alignment.
+ * ========================================================================================== */
+typedef struct kde_reg_params { float z_min, z_max; int max_splat; } kde_reg_params;
+typedef struct kde_reg kde_reg;
+/* Kinect.cpp:71-75 takes no parameter: z_min 0, z_max FLT_MAX, max_splat 0 */
+int kde_reg_default_params(kde_reg_params* p);
+/* the two viewpoints of Kinect.cpp:71-75 -- depth frames of depth_w x depth_h, colour frames of color_w x color_h -- for
+ * max_batch frames on the current device; p == NULL: the defaults.  Sizes >= 1 (a side at most 2^24); z_min finite and >= 0
+ * (the key order needs positive z), z_min < z_max, max_splat in 0..16.  The object owns the z-buffer (4 bytes per target
+ * pixel), filled[max_batch] and max_batch * color_w * color_h floats for calls with out_dev == NULL.  On a host without a
+ * device the object is created without buffers: every call validates as usual and the launches then return KDE_ERR_HIP. */
+int kde_reg_create(kde_reg** out, int depth_w, int depth_h, int color_w, int color_h, int max_batch, const kde_reg_params* p);
+int kde_reg_destroy(kde_reg* h);   /* Kinect.cpp:71-75 keeps its generators while the Kinect lives; NULL is a no-op */
+/* the calibration Kinect.cpp:71-75 leaves to the device's factory data: Kd9, Kc9, R9 row-major, t3 in millimetres, as above.
+ * KDE_ERR_INVALID: a null pointer, a non-finite value (as double or as float), fx or fy of either camera not > 0. */
+int kde_reg_set_calibration(kde_reg* h, const double* Kd9, const double* Kc9, const double* R9, const double* t3);
+/* Kinect.cpp:71-75 for n <= max_batch frames: depth_dev is [n][depth_h][depth_w] of depth_format (KDE_DEPTH_F32 |
+ * KDE_DEPTH_U16), out_dev is [n][color_h][color_w] of out_format or NULL for the object-owned buffer.  Pointers need the
+ * alignment of their element only; source frames on a 16-byte (float) or 8-byte (uint16) boundary are read with vector
+ * loads, with the same result.  KDE_ERR_INVALID before kde_reg_set_calibration.  Three launches (the z-buffer reset to
+ * 0xFF, the scatter, the finalise); no allocation, no host synchronisation, no communication between workgroups: capturable
+ * like kde_cloud_build_batch.  The reset is a kernel and not a memset node, because the replay of a captured graph did not
+ * keep a memset node in front of the kernel behind it. */
+int kde_reg_register_batch(kde_reg* h, int n, const void* depth_dev, int depth_format, int out_format, void* out_dev, void* stream);
+/* Kinect.cpp:71-75 the other way round, for users who would rather work at the depth camera's resolution: for each depth
+ * pixel (u, v) of frame f with the point-mode target (iu, iv) of its centre, out_bgr[f][v][u] = bgr[iv][iu] when the pixel
+ * is valid and its target inside the colour frame, else (0, 0, 0).  bgr_dev is [bgr_frames][color_h][color_w][3] with
+ * bgr_frames == 1 (one image for every frame) or n; out_bgr_dev is [n][depth_h][depth_w][3].  THERE IS NO OCCLUSION TEST: a
+ * depth pixel the colour camera cannot see takes the colour of whatever hides it.  One launch; does not touch the z-buffer
+ * or the results of kde_reg_register_batch. */
+int kde_reg_color_to_depth_batch(kde_reg* h, int n, const void* depth_dev, int depth_format, const uint8_t* bgr_dev, int bgr_frames,
+                                 uint8_t* out_bgr_dev, void* stream);
+/* the registered frames of the last kde_reg_register_batch (Kinect.cpp:71-75): out_dev of that call or the object-owned
+ * buffer, in that call's out_format; valid until the next call or destroy.  KDE_ERR_INVALID before the first call. */
+int kde_reg_depth_device(kde_reg* h, void** out);
+/* the same in pinned host memory after a blocking copy on `stream` (Kinect.cpp:71-75 hands its frames to the host):
+ * synchronises; out_dev of the last call must still be alive */
+int kde_reg_depth_host(kde_reg* h, void* stream, const void** out);
+int kde_reg_filled_device(kde_reg* h, uint32_t** out);   /* Kinect.cpp:71-75: filled[n] of the last call, on the device */
+/* filled[n] in pinned host memory after a blocking copy on `stream` (Kinect.cpp:71-75): synchronises */
+int kde_reg_filled_host(kde_reg* h, void* stream, const uint32_t** out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -95,6 +95,16 @@ class CloudPoint(C.Structure):
     _fields_ = [("x", C.c_float), ("y", C.c_float), ("z", C.c_float), ("rgb", C.c_uint32)]
 
 
+class RegHandle(C.c_void_p):
+    """kde_reg*: a ctypes type of its own, like CloudHandle, which keeps the kde_reg_* entry points out of the frozen record
+    tools/abi_refusals.py enumerates; tests/test_reg_abi.py checks their refusals."""
+
+
+class RegParams(C.Structure):
+    """kde_reg_params (defaults: 0, FLT_MAX, 0 -- every finite positive depth, one target pixel per source pixel)."""
+    _fields_ = [("z_min", C.c_float), ("z_max", C.c_float), ("max_splat", C.c_int)]
+
+
 def build(force: bool = False) -> str:
     """Compile libkde_hip.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     if force:
@@ -274,6 +284,16 @@ SIGNATURES = {
     "kde_cloud_counts_device": (_i, [CloudHandle, _pp]),
     "kde_cloud_counts_host": (_i, [CloudHandle, _vp, _pp]),
     "kde_cloud_points_host": (_i, [CloudHandle, _vp, _pp, _pp]),
+    "kde_reg_default_params": (_i, [C.POINTER(RegParams)]),
+    "kde_reg_create": (_i, [C.POINTER(RegHandle), _i, _i, _i, _i, _i, C.POINTER(RegParams)]),
+    "kde_reg_destroy": (_i, [RegHandle]),
+    "kde_reg_set_calibration": (_i, [RegHandle, _vp, _vp, _vp, _vp]),
+    "kde_reg_register_batch": (_i, [RegHandle, _i, _vp, _i, _i, _vp, _vp]),
+    "kde_reg_color_to_depth_batch": (_i, [RegHandle, _i, _vp, _i, _vp, _i, _vp, _vp]),
+    "kde_reg_depth_device": (_i, [RegHandle, _pp]),
+    "kde_reg_depth_host": (_i, [RegHandle, _vp, _pp]),
+    "kde_reg_filled_device": (_i, [RegHandle, _pp]),
+    "kde_reg_filled_host": (_i, [RegHandle, _vp, _pp]),
 }
 
 

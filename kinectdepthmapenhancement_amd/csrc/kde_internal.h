@@ -226,6 +226,33 @@ struct CloudLaunch {
 };
 int launch_cloud(const CloudLaunch& a, hipStream_t s);
 
+// DepthRegistration (reg_kernels.hip): what Kinect.cpp:71-75 asks OpenNI for -- the depth map as the colour camera sees it
+struct RegCalib {
+    float fxd, fyd, cxd, cyd;                      // depth camera; cx, cy stay floats (not truncated as DimensionConvertor does)
+    float fxc, fyc, cxc, cyc;                      // colour camera
+    float r[9], t[3];                              // P_colour = R * P_depth + t, millimetres
+};
+constexpr int kRegMaxSplat = 16;
+constexpr int kRegMaxSide = 1 << 24;               // W - 1 and H - 1 of either camera are exact floats
+// keys per frame of the z-buffer: the frame's pixels rounded up to whole octets, so every frame starts on a 32-byte boundary
+__host__ __device__ constexpr size_t reg_zstride(size_t color_px) { return (color_px + 7) & ~(size_t)7; }
+struct RegLaunch {
+    int n;
+    const void* depth;                             // [n][hd][wd] float or uint16
+    int depth_format;                              // KDE_DEPTH_*
+    int wd, hd, wc, hc;
+    RegCalib c;
+    float z_min, z_max;
+    int max_splat;                                 // 0: point mode
+    uint32_t* zbuf;                                // [n][reg_zstride(wc * hc)] keys (register only)
+    uint32_t* filled;                              // [n] (register only)
+    void* out;                                     // [n][hc][wc] float or uint16 (register only)
+    int out_format;                                // KDE_DEPTH_*
+};
+int launch_reg(const RegLaunch& a, hipStream_t s);
+// the companion gather: out [n][hd][wd][3] from bgr [bgr_frames][hc][wc][3]
+int launch_reg_gather(const RegLaunch& a, const uint8_t* bgr, int bgr_frames, uint8_t* out, hipStream_t s);
+
 struct DaspGeom {
     int width, height, rows, cols, wx, wy;
 };

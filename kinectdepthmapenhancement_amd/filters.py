@@ -967,6 +967,108 @@ class PointCloudXYZRGB(_Handle):
         return [raw[int(offsets[f]):int(offsets[f + 1])] for f in range(self._n)]
 
 
+class DepthRegistration(_Handle):
+    """What Kinect::InitAllData (Kinect.cpp:71-75) asks OpenNI for, on the device (kde_reg_*): depth frames warped into the
+    colour camera's view, so that depth pixel (x, y) and colour pixel (x, y) look along the same ray, as every other class
+    here assumes.  depth_size and color_size are (width, height); params is a RegParams (z_min, z_max, max_splat) or None
+    for the defaults (0, FLT_MAX, point mode).  The rule is stated in include/kde_hip.h: a scatter through a z-buffer, the
+    nearest source pixel wins, deterministic to the bit; cx and cy are kept as floats, there is no lens distortion."""
+    _destroy = "kde_reg_destroy"
+    _handle_type = _native.RegHandle
+
+    def __init__(self, depth_size, color_size, max_batch: int = 1, params: Optional["_native.RegParams"] = None):
+        super().__init__()
+        (self.depth_width, self.depth_height), (self.color_width, self.color_height) = depth_size, color_size
+        self.max_batch = max_batch
+        self._n, self._fmt = 0, _native.KDE_DEPTH_F32
+        check(lib().kde_reg_create(C.byref(self._h), self.depth_width, self.depth_height, self.color_width, self.color_height,
+                                   max_batch, None if params is None else C.byref(params)))
+
+    @staticmethod
+    def default_params() -> "_native.RegParams":
+        p = _native.RegParams()
+        check(lib().kde_reg_default_params(C.byref(p)))
+        return p
+
+    def set_calibration(self, Kd, Kc, R, t) -> None:
+        """Kd, Kc, R: 3 x 3 (row-major); t: 3 values in millimetres; P_colour = R * P_depth + t"""
+        kd, kc, r = _K9(Kd), _K9(Kc), _K9(R)
+        tt = np.ascontiguousarray(np.asarray(t, np.float64).reshape(3))
+        check(lib().kde_reg_set_calibration(self._h, kd.ctypes.data, kc.ctypes.data, r.ctypes.data, tt.ctypes.data))
+
+    def _depth_format(self, depth: torch.Tensor):
+        if not isinstance(depth, torch.Tensor) or not depth.is_cuda:
+            raise TypeError("depth: expected a CUDA tensor")
+        if depth.dim() != 3 or tuple(depth.shape[1:]) != (self.depth_height, self.depth_width) or not depth.is_contiguous() or \
+                depth.dtype not in (torch.float32, torch.int16, _U16):
+            raise ValueError(f"depth: expected contiguous float32 / uint16 [n,{self.depth_height},{self.depth_width}], got "
+                             f"{depth.dtype} {tuple(depth.shape)}")
+        return depth.shape[0], (_native.KDE_DEPTH_F32 if depth.dtype == torch.float32 else _native.KDE_DEPTH_U16)
+
+    def register(self, depth: torch.Tensor, out: Optional[torch.Tensor] = None, out_format=torch.float32) -> torch.Tensor:
+        """depth: [n,Hd,Wd] float32, or uint16 / int16 holding the sensor's uint16.  out: [n,Hc,Wc] float32 or uint16 / int16
+        (its dtype is the output format), or None for the object-owned buffer in out_format (torch.float32, torch.uint16 or
+        torch.int16).  Returns the registered frames (0 where no source pixel came).  Asynchronous on torch's current stream;
+        no allocation, copy or synchronisation on the device."""
+        n, fmt = self._depth_format(depth)
+        dt = out.dtype if isinstance(out, torch.Tensor) else out_format
+        if dt == torch.float32:
+            ofmt = _native.KDE_DEPTH_F32
+        elif dt is not None and dt in (torch.int16, _U16):
+            ofmt = _native.KDE_DEPTH_U16
+        else:
+            raise ValueError(f"out_format: expected torch.float32 or torch.uint16, got {dt}")
+        if out is not None:
+            _req(out, dt, (n, self.color_height, self.color_width), "out")
+        check(lib().kde_reg_register_batch(self._h, n, depth.data_ptr(), fmt, ofmt, _ptr(out), _stream()))
+        self._n, self._fmt = n, ofmt
+        return out if out is not None else self.depth_device()
+
+    def depth_device(self) -> torch.Tensor:
+        """the frames of the last register(): `out` of that call or the object-owned buffer, [n,Hc,Wc] float32, or int16
+        holding the uint16 bits (`.cpu().numpy().view(numpy.uint16)`)"""
+        p = C.c_void_p()
+        check(lib().kde_reg_depth_device(self._h, C.byref(p)))
+        if self._fmt == _native.KDE_DEPTH_F32:
+            return _view(p.value, (self._n, self.color_height, self.color_width), torch.float32, self)
+        return _view(p.value, (self._n, self.color_height, self.color_width * 2), torch.uint8, self).view(torch.int16)
+
+    def depth_host(self) -> np.ndarray:
+        """the same as a numpy array, float32 or uint16; synchronises torch's current stream"""
+        p = C.c_void_p()
+        check(lib().kde_reg_depth_host(self._h, _stream(), C.byref(p)))
+        ctype, dtype = (C.c_float, np.float32) if self._fmt == _native.KDE_DEPTH_F32 else (C.c_uint16, np.uint16)
+        shape = (self._n, self.color_height, self.color_width)
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(ctype)), shape=shape).astype(dtype, copy=True)
+
+    def filled(self) -> np.ndarray:
+        """the number of target pixels reached per frame of the last register(), uint32 [n]; synchronises torch's current stream"""
+        p = C.c_void_p()
+        check(lib().kde_reg_filled_host(self._h, _stream(), C.byref(p)))
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint32)), shape=(self._n,)).copy()
+
+    def filled_device(self) -> torch.Tensor:
+        """the same on the device, as raw bytes [n, 4] (uint32), a view of the object-owned buffer"""
+        p = C.c_void_p()
+        check(lib().kde_reg_filled_device(self._h, C.byref(p)))
+        return _view(p.value, (self._n, 4), torch.uint8, self)
+
+    def color_to_depth(self, depth: torch.Tensor, bgr: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """the companion gather: bgr uint8 [n,Hc,Wc,3] or [1,Hc,Wc,3] as the depth camera sees it, uint8 [n,Hd,Wd,3]: the colour
+        at the point-mode target of each valid depth pixel, (0, 0, 0) elsewhere.  No occlusion test."""
+        n, fmt = self._depth_format(depth)
+        if not isinstance(bgr, torch.Tensor) or bgr.dim() != 4 or bgr.shape[0] not in (1, n):
+            raise ValueError(f"bgr: expected [1 or {n},{self.color_height},{self.color_width},3] uint8")
+        _req(bgr, torch.uint8, (bgr.shape[0], self.color_height, self.color_width, 3), "bgr")
+        if out is None:
+            out = torch.empty((n, self.depth_height, self.depth_width, 3), dtype=torch.uint8, device=depth.device)
+        else:
+            _req(out, torch.uint8, (n, self.depth_height, self.depth_width, 3), "out")
+        check(lib().kde_reg_color_to_depth_batch(self._h, n, depth.data_ptr(), fmt, bgr.data_ptr(), bgr.shape[0], out.data_ptr(),
+                                                 _stream()))
+        return out
+
+
 COMPARE_METHODS = ("input", "jbf", "mrf", "rgbf", "kde")
 
 
