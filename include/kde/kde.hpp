@@ -19,6 +19,7 @@
 //   kde::MeanError3D              (extension: the quality figure of main.cpp:220-308 for a batch, on the device)
 //   kde::PointCloudXYZRGB         (extension: the coloured clouds of main.cpp:211-300 for a batch, compacted on the device)
 //   kde::DepthRegistration        (extension: what Kinect.cpp:71-75 asks OpenNI for -- depth warped into the colour camera's view)
+//   kde::LensUndistortion         (extension: frames of a camera with lens distortion resampled into the pinhole view assumed above)
 //
 // What differs from the reference headers, and why:
 //   * cv::gpu::GpuMat parameters are templates over "anything with .data/.rows/.cols/.step" — a real
@@ -1280,6 +1281,101 @@ private:
     static int format(const float*) { return KDE_DEPTH_F32; }
     static int format(const uint16_t*) { return KDE_DEPTH_U16; }
     kde_reg* h_ = nullptr;
+    void* stream_ = nullptr;
+};
+
+// extension (no reference counterpart): frames of a camera with lens distortion -- OpenCV's rational model k1, k2, p1, p2, k3,
+// k4, k5, k6, of which Brown-Conrady is k4 = k5 = k6 = 0 -- resampled into a pinhole view on the device (kde_undist_*), so that
+// sensors calibrated with OpenCV can feed every class above, DepthRegistration first.  The rule is stated in kde_hip.h: colour
+// is bilinear with (0, 0, 0) outside the source; depth takes the nearest valid sample or, with depth_interp 1, the bilinear
+// value where the four taps are valid and within max_gap of each other; deterministic to the bit; no rectifying rotation.
+// undistortColor() and undistortDepth() are asynchronous on the object's stream and capturable; the *_Host members synchronise.
+class LensUndistortion {
+public:
+    static kde_undist_params defaultParams()
+    {
+        kde_undist_params p{};
+        check(kde_undist_default_params(&p));
+        return p;
+    }
+    LensUndistortion(int src_width, int src_height, int out_width, int out_height, int max_batch = 1)
+    {
+        check(kde_undist_create(&h_, src_width, src_height, out_width, out_height, max_batch, nullptr));
+    }
+    LensUndistortion(int src_width, int src_height, int out_width, int out_height, int max_batch, const kde_undist_params& params)
+    {
+        check(kde_undist_create(&h_, src_width, src_height, out_width, out_height, max_batch, &params));
+    }
+    ~LensUndistortion() { kde_undist_destroy(h_); }
+    LensUndistortion(const LensUndistortion&) = delete;
+    LensUndistortion& operator=(const LensUndistortion&) = delete;
+
+    // the distorted camera's intrinsic matrix and dist8 = k1, k2, p1, p2, k3, k4, k5, k6; the pinhole view keeps the matrix
+    template <class MatLike>
+    void setCalibration(const MatLike& intrinsic, const double* dist8)
+    {
+        double k[9];
+        intrinsic_to_array(intrinsic, k);
+        check(kde_undist_set_calibration(h_, k, dist8, nullptr));
+    }
+    // the same with a camera matrix of its own for the pinhole view (OpenCV's getOptimalNewCameraMatrix, another size, ...)
+    template <class MatLike>
+    void setCalibration(const MatLike& intrinsic, const double* dist8, const MatLike& new_intrinsic)
+    {
+        double k[9], kn[9];
+        intrinsic_to_array(intrinsic, k);
+        intrinsic_to_array(new_intrinsic, kn);
+        check(kde_undist_set_calibration(h_, k, dist8, kn));
+    }
+    // n frames back to back; bgr_frames = 1 (one image for every frame) or n
+    void undistortColor(int n, const uint8_t* bgr_device, int bgr_frames, uint8_t* out_bgr_device)
+    {
+        check(kde_undist_color_batch(h_, n, bgr_device, bgr_frames, out_bgr_device, stream_));
+    }
+    // n frames back to back; the output format is the type of out_device (nullptr of that type: the object-owned buffer)
+    template <class Depth, class Out>
+    void undistortDepth(int n, const Depth* depth_device, Out* out_device)
+    {
+        check(kde_undist_depth_batch(h_, n, depth_device, format(depth_device), format(out_device), out_device, stream_));
+    }
+    void* depth_Device() const
+    {
+        void* p = nullptr;
+        check(kde_undist_depth_device(h_, &p));
+        return p;
+    }
+    const void* depth_Host() const
+    {
+        const void* p = nullptr;
+        check(kde_undist_depth_host(h_, stream_, &p));
+        return p;
+    }
+    uint32_t* filled_Device() const
+    {
+        uint32_t* p = nullptr;
+        check(kde_undist_filled_device(h_, &p));
+        return p;
+    }
+    const uint32_t* filled_Host() const
+    {
+        const uint32_t* p = nullptr;
+        check(kde_undist_filled_host(h_, stream_, &p));
+        return p;
+    }
+    // [out_height][out_width] of (us, vs): OpenCV's initUndistortRectifyMap product, computed at the first request
+    const float* map_Device() const
+    {
+        const float* p = nullptr;
+        check(kde_undist_map_device(h_, stream_, &p));
+        return p;
+    }
+    void setStream(void* hip_stream) { stream_ = hip_stream; }
+    kde_undist* handle() const { return h_; }
+
+private:
+    static int format(const float*) { return KDE_DEPTH_F32; }
+    static int format(const uint16_t*) { return KDE_DEPTH_U16; }
+    kde_undist* h_ = nullptr;
     void* stream_ = nullptr;
 };
 

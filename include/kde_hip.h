@@ -670,7 +670,8 @@ int kde_cloud_points_host(kde_cloud* h, void* stream, const kde_cloud_point** ou
  * double matrix converted to float, and P_colour = R * P_depth + t (R 9 doubles row-major, t 3 doubles in millimetres, both
  * converted to float).  Axes: x right, y down, z forward; pixel centres at integer coordinates.  cx AND cy ARE KEPT AS
  * FLOATS HERE, not truncated to int as DimensionConvertor does (DimensionConvertor.cpp:3-13): calibrated principal points
- * are no integers, and truncating two cameras independently would move the result by up to a pixel.  No lens distortion.
+ * are no integers, and truncating two cameras independently would move the result by up to a pixel.  No lens distortion
+ * here: frames of a camera with distortion coefficients go through LensUndistortion (kde_undist_*, below) first.
  *
  * The rule.  Every operation is one IEEE binary32 operation in the order written, no fused multiply-add, divisions
  * correctly rounded.  For source pixel (u, v) of frame f with depth z (float, or (float)u16):
@@ -734,6 +735,89 @@ int kde_reg_depth_host(kde_reg* h, void* stream, const void** out);
 int kde_reg_filled_device(kde_reg* h, uint32_t** out);   /* Kinect.cpp:71-75: filled[n] of the last call, on the device */
 /* filled[n] in pinned host memory after a blocking copy on `stream` (Kinect.cpp:71-75): synchronises */
 int kde_reg_filled_host(kde_reg* h, void* stream, const uint32_t** out);
+
+/* ==========================================================================================
+ * LensUndistortion: frames of a camera with lens distortion resampled into a pinhole view.  Every class of this library
+ * assumes a pinhole camera (DimensionConvertor.cpp:3-13 back-projects with fx, fy, cx, cy only); the reference never had to
+ * care, because its frames come through OpenNI from a Kinect v1.  Sensors calibrated with OpenCV ship distortion
+ * coefficients, and their frames, taken as they are, bend every plane the pipeline fits.  This is a gather, for a batch on
+ * the device: colour and depth go through the same map with different sampling rules.  No reference counterpart.
+ *
+ * Calibration: the source (distorted) camera (fx, fy, cx, cy) from a row-major 3 x 3 double matrix K converted to float (cx,
+ * cy stay floats, as in kde_reg_*); eight coefficients k1, k2, p1, p2, k3, k4, k5, k6 in OpenCV's order, doubles converted to
+ * float: the rational model, of which k4 = k5 = k6 = 0 is the five-coefficient Brown-Conrady model; the target (pinhole)
+ * camera (fxn, fyn, cxn, cyn) from K_new, or K when K_new is NULL.  Source frames are src_w x src_h, output frames out_w x
+ * out_h.  There is no rectifying rotation: it would change z, which is kde_reg_*'s job.  No fisheye model.
+ *
+ * The rule.  Every operation is one IEEE binary32 operation in the order written, no fused multiply-add, divisions
+ * correctly rounded.  For output pixel (i, j):
+ *   x  = ((float)i - cxn) / fxn;  y = ((float)j - cyn) / fyn
+ *   xx = x * x;  yy = y * y;  xy = x * y;  r2 = xx + yy
+ *   num = ((k3 * r2 + k2) * r2 + k1) * r2 + 1;  den = ((k6 * r2 + k5) * r2 + k4) * r2 + 1;  rad = num / den
+ *   xd = (x * rad + p1 * (xy + xy)) + p2 * (r2 + (xx + xx))
+ *   yd = (y * rad + p1 * (r2 + (yy + yy))) + p2 * (xy + xy)
+ *   us = fx * xd + cx;  vs = fy * yd + cy                      the point of the source frame the pixel shows
+ *   bilinear(p)  x0 = floorf(us), ax = us - x0, y0 = floorf(vs), ay = vs - y0; the taps p00 = p(x0, y0), p01 = p(x0 + 1, y0),
+ *             p10 = p(x0, y0 + 1), p11 = p(x0 + 1, y0 + 1); top = p00 + ax * (p01 - p00), bot = p10 + ax * (p11 - p10),
+ *             value = top + ay * (bot - top)
+ *   colour    BGR uint8.  The pixel is (0, 0, 0) unless us > -1 && us < src_w && vs > -1 && vs < src_h, tested on the floats
+ *             before any conversion to an integer (a NaN fails).  A tap outside the source frame is (0, 0, 0).  Per channel
+ *             the byte stored is rintf(bilinear) (ties to even) clamped to 0 .. 255.
+ *   depth     KDE_DEPTH_F32 or KDE_DEPTH_U16 on either side, uint16 widened by (float)u.  A depth is valid iff z > z_min && z <
+ *             z_max (defaults 0 and FLT_MAX: NaN, +-inf, 0 and negatives are invalid).
+ *             depth_interp == 0 (default), and the fall-back of the other mode: fu = rintf(us), fv = rintf(vs) (ties to
+ *             even); the sample (fu, fv) is kept iff fu >= 0 && fu <= src_w - 1 && fv >= 0 && fv <= src_h - 1, tested on the
+ *             floats, and it is valid; otherwise the pixel is 0 (the sensor's "invalid").
+ *             depth_interp == 1: the pixel is bilinear(z) iff x0 >= 0 && x0 + 1 <= src_w - 1 && y0 >= 0 && y0 + 1 <= src_h - 1
+ *             (all four taps inside, on the floats), all four taps are valid, and max - min of the four <= max_gap
+ *             (millimetres; no default).  In every other case the nearest rule above: a depth is never blended across a hole
+ *             or an edge.
+ *             The output is the float itself (KDE_DEPTH_F32) or depth_to_u16 of it as kde_points_to_depth rounds
+ *             (KDE_DEPTH_U16).  filled[f] = the number of output pixels of frame f that were kept (by either rule), counted
+ *             before the uint16 rounding, as kde_reg_* counts its keys.
+ * Every output pixel is a function of the source frame and its own coordinates, and the count is an integer sum: the result
+ * is deterministic to the bit and does not depend on n, a frame's position in the batch or pointer alignment.
+ * ========================================================================================== */
+typedef struct kde_undist_params { float z_min, z_max; int depth_interp; float max_gap; } kde_undist_params;
+typedef struct kde_undist kde_undist;
+/* z_min 0, z_max FLT_MAX, depth_interp 0 (nearest), max_gap 0 (unused in that mode; depth_interp 1 needs one) */
+int kde_undist_default_params(kde_undist_params* p);
+/* source frames of src_w x src_h, output frames of out_w x out_h, max_batch frames on the current device; p == NULL: the
+ * defaults.  Sizes >= 1 (a side at most 2^24, so that W - 1 is an exact float); z_min finite and >= 0, z_min < z_max,
+ * depth_interp 0 or 1, and with depth_interp 1 a finite max_gap > 0.  The object owns filled[max_batch], max_batch * out_w *
+ * out_h floats for calls with out_dev == NULL and the out_w * out_h float2 of kde_undist_map_device.  On a host without a
+ * device the object is created without buffers: every call validates as usual and the launches then return KDE_ERR_HIP. */
+int kde_undist_create(kde_undist** out, int src_w, int src_h, int out_w, int out_h, int max_batch, const kde_undist_params* p);
+int kde_undist_destroy(kde_undist* h);   /* NULL is a no-op */
+/* K9 and Knew9 row-major 3 x 3 (Knew9 == NULL: the pinhole view keeps K), dist8 = k1, k2, p1, p2, k3, k4, k5, k6, as above.
+ * KDE_ERR_INVALID: a null K9 or dist8, a non-finite value (as double or as float), fx or fy of either camera not > 0.  A
+ * refused call leaves the calibration in force as it was. */
+int kde_undist_set_calibration(kde_undist* h, const double* K9, const double* dist8, const double* Knew9);
+/* n <= max_batch colour frames: bgr_dev is [bgr_frames][src_h][src_w][3] with bgr_frames == 1 (one image for every frame) or
+ * n, out_bgr_dev is [n][out_h][out_w][3].  No alignment is asked of either pointer; output frames on a 4-byte boundary are
+ * written 256 consecutive bytes per store instruction, with the same result.  KDE_ERR_INVALID before
+ * kde_undist_set_calibration.  One launch; no allocation, no host synchronisation, no communication between workgroups:
+ * capturable like kde_reg_register_batch. */
+int kde_undist_color_batch(kde_undist* h, int n, const uint8_t* bgr_dev, int bgr_frames, uint8_t* out_bgr_dev, void* stream);
+/* n <= max_batch depth frames: depth_dev is [n][src_h][src_w] of depth_format (KDE_DEPTH_F32 | KDE_DEPTH_U16), out_dev is
+ * [n][out_h][out_w] of out_format or NULL for the object-owned buffer.  Pointers need the alignment of their element only;
+ * output frames on a 16-byte (float) or 8-byte (uint16) boundary are written with vector stores, with the same result.
+ * KDE_ERR_INVALID before kde_undist_set_calibration.  Two launches (filled = 0, the remap: kernel nodes keep their order in a
+ * replayed graph, a memset node did not); no allocation, no host synchronisation: capturable. */
+int kde_undist_depth_batch(kde_undist* h, int n, const void* depth_dev, int depth_format, int out_format, void* out_dev, void* stream);
+/* the frames of the last kde_undist_depth_batch: out_dev of that call or the object-owned buffer, in that call's
+ * out_format; valid until the next call or destroy.  KDE_ERR_INVALID before the first call. */
+int kde_undist_depth_device(kde_undist* h, void** out);
+/* the same in pinned host memory after a blocking copy on `stream`: synchronises; out_dev of the last call must still be alive */
+int kde_undist_depth_host(kde_undist* h, void* stream, const void** out);
+int kde_undist_filled_device(kde_undist* h, uint32_t** out);   /* filled[n] of the last kde_undist_depth_batch, on the device */
+/* filled[n] in pinned host memory after a blocking copy on `stream`: synchronises */
+int kde_undist_filled_host(kde_undist* h, void* stream, const uint32_t** out);
+/* [out_h][out_w] of (us, vs) as float2 on the device, what OpenCV's initUndistortRectifyMap gives (CV_32FC2) for this
+ * calibration with R = identity: computed by its own launch on `stream` at the first request after
+ * kde_undist_set_calibration, returned as it is later (work on another stream must be ordered behind that first request by
+ * the caller).  The remap calls above compute the map per pixel and do not read it.  No allocation, no synchronisation. */
+int kde_undist_map_device(kde_undist* h, void* stream, const float** out);
 
 #ifdef __cplusplus
 }

@@ -105,6 +105,16 @@ class RegParams(C.Structure):
     _fields_ = [("z_min", C.c_float), ("z_max", C.c_float), ("max_splat", C.c_int)]
 
 
+class UndistHandle(C.c_void_p):
+    """kde_undist*: a ctypes type of its own, like CloudHandle and RegHandle, which keeps the kde_undist_* entry points out of
+    the frozen record tools/abi_refusals.py enumerates; tests/test_undist_abi.py checks their refusals."""
+
+
+class UndistParams(C.Structure):
+    """kde_undist_params (defaults: 0, FLT_MAX, 0, 0 -- every finite positive depth, the nearest sample)."""
+    _fields_ = [("z_min", C.c_float), ("z_max", C.c_float), ("depth_interp", C.c_int), ("max_gap", C.c_float)]
+
+
 def build(force: bool = False) -> str:
     """Compile libkde_hip.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     if force:
@@ -294,6 +304,17 @@ SIGNATURES = {
     "kde_reg_depth_host": (_i, [RegHandle, _vp, _pp]),
     "kde_reg_filled_device": (_i, [RegHandle, _pp]),
     "kde_reg_filled_host": (_i, [RegHandle, _vp, _pp]),
+    "kde_undist_default_params": (_i, [C.POINTER(UndistParams)]),
+    "kde_undist_create": (_i, [C.POINTER(UndistHandle), _i, _i, _i, _i, _i, C.POINTER(UndistParams)]),
+    "kde_undist_destroy": (_i, [UndistHandle]),
+    "kde_undist_set_calibration": (_i, [UndistHandle, _vp, _vp, _vp]),
+    "kde_undist_color_batch": (_i, [UndistHandle, _i, _vp, _i, _vp, _vp]),
+    "kde_undist_depth_batch": (_i, [UndistHandle, _i, _vp, _i, _i, _vp, _vp]),
+    "kde_undist_depth_device": (_i, [UndistHandle, _pp]),
+    "kde_undist_depth_host": (_i, [UndistHandle, _vp, _pp]),
+    "kde_undist_filled_device": (_i, [UndistHandle, _pp]),
+    "kde_undist_filled_host": (_i, [UndistHandle, _vp, _pp]),
+    "kde_undist_map_device": (_i, [UndistHandle, _vp, _pp]),
 }
 
 

@@ -253,6 +253,30 @@ int launch_reg(const RegLaunch& a, hipStream_t s);
 // the companion gather: out [n][hd][wd][3] from bgr [bgr_frames][hc][wc][3]
 int launch_reg_gather(const RegLaunch& a, const uint8_t* bgr, int bgr_frames, uint8_t* out, hipStream_t s);
 
+// LensUndistortion (undist_kernels.hip): distorted frames resampled into a pinhole view, a gather
+struct UndistCalib {
+    float fx, fy, cx, cy;                          // the source (distorted) camera; cx, cy stay floats
+    float fxn, fyn, cxn, cyn;                      // the target (pinhole) camera
+    float k1, k2, p1, p2, k3, k4, k5, k6;          // OpenCV's order (the rational model; k4..k6 = 0: Brown-Conrady)
+};
+struct UndistLaunch {
+    int n;
+    int sw, sh, ow, oh;                            // source and output frame
+    UndistCalib c;
+    float z_min, z_max;                            // depth only
+    int depth_interp;                              // 0: nearest, 1: guarded bilinear
+    float max_gap;
+    const void* depth;                             // [n][sh][sw] float or uint16 (depth only)
+    int depth_format;                              // KDE_DEPTH_*
+    void* out;                                     // [n][oh][ow] float or uint16 (depth only)
+    int out_format;                                // KDE_DEPTH_*
+    uint32_t* filled;                              // [n] (depth only)
+};
+// out [n][oh][ow][3] from bgr [bgr_frames][sh][sw][3]
+int launch_undist_color(const UndistLaunch& a, const uint8_t* bgr, int bgr_frames, uint8_t* out, hipStream_t s);
+int launch_undist_depth(const UndistLaunch& a, hipStream_t s);          // 2 kernels: filled = 0, the remap
+int launch_undist_map(const UndistLaunch& a, float2* map, hipStream_t s);   // map [oh][ow] of (us, vs)
+
 struct DaspGeom {
     int width, height, rows, cols, wx, wy;
 };

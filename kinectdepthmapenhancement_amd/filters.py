@@ -1069,6 +1069,124 @@ class DepthRegistration(_Handle):
         return out
 
 
+class LensUndistortion(_Handle):
+    """Frames of a camera with lens distortion resampled into the pinhole view every other class here assumes, on the device
+    (kde_undist_*): OpenCV's rational model (k1, k2, p1, p2, k3, k4, k5, k6; zeros for k4..k6 give Brown-Conrady), no
+    rectifying rotation.  src_size and out_size are (width, height); params is an UndistParams (z_min, z_max, depth_interp,
+    max_gap) or None for the defaults (0, FLT_MAX, nearest).  The rule is stated in include/kde_hip.h: colour is bilinear
+    with (0, 0, 0) outside the source, depth is the nearest valid sample or, with depth_interp 1, bilinear where the four
+    taps are valid and within max_gap of each other; deterministic to the bit."""
+    _destroy = "kde_undist_destroy"
+    _handle_type = _native.UndistHandle
+
+    def __init__(self, src_size, out_size=None, max_batch: int = 1, params: Optional["_native.UndistParams"] = None):
+        super().__init__()
+        self.src_width, self.src_height = src_size
+        self.out_width, self.out_height = out_size if out_size is not None else src_size
+        self.max_batch = max_batch
+        self._n, self._fmt = 0, _native.KDE_DEPTH_F32
+        check(lib().kde_undist_create(C.byref(self._h), self.src_width, self.src_height, self.out_width, self.out_height,
+                                      max_batch, None if params is None else C.byref(params)))
+
+    @staticmethod
+    def default_params() -> "_native.UndistParams":
+        p = _native.UndistParams()
+        check(lib().kde_undist_default_params(C.byref(p)))
+        return p
+
+    def set_calibration(self, K, dist, K_new=None) -> None:
+        """K, K_new: 3 x 3 (row-major), K_new None for K; dist: k1, k2, p1, p2, k3[, k4, k5, k6] (4, 5 or 8 values as OpenCV
+        hands them out; the missing ones are 0)"""
+        d = np.asarray(dist, np.float64).reshape(-1)
+        if d.size not in (4, 5, 8):
+            raise ValueError(f"dist: expected 4, 5 or 8 coefficients, got {d.size}")
+        d8 = np.zeros(8, np.float64)
+        d8[:d.size] = d
+        k = _K9(K)
+        kn = None if K_new is None else _K9(K_new)
+        check(lib().kde_undist_set_calibration(self._h, k.ctypes.data, d8.ctypes.data, None if kn is None else kn.ctypes.data))
+
+    def color(self, bgr: torch.Tensor, n: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """bgr: uint8 [n,Hs,Ws,3], or [1,Hs,Ws,3] with n given (one image for every frame).  Returns uint8 [n,Ho,Wo,3].
+        Asynchronous on torch's current stream."""
+        if not isinstance(bgr, torch.Tensor) or bgr.dim() != 4:
+            raise ValueError(f"bgr: expected [n,{self.src_height},{self.src_width},3] uint8")
+        n = bgr.shape[0] if n is None else n
+        if bgr.shape[0] not in (1, n):
+            raise ValueError(f"bgr: expected 1 or {n} frames, got {bgr.shape[0]}")
+        _req(bgr, torch.uint8, (bgr.shape[0], self.src_height, self.src_width, 3), "bgr")
+        if out is None:
+            out = torch.empty((n, self.out_height, self.out_width, 3), dtype=torch.uint8, device=bgr.device)
+        else:
+            _req(out, torch.uint8, (n, self.out_height, self.out_width, 3), "out")
+        check(lib().kde_undist_color_batch(self._h, n, bgr.data_ptr(), bgr.shape[0], out.data_ptr(), _stream()))
+        return out
+
+    def depth(self, depth: torch.Tensor, out: Optional[torch.Tensor] = None, out_format=torch.float32) -> torch.Tensor:
+        """depth: [n,Hs,Ws] float32, or uint16 / int16 holding the sensor's uint16.  out: [n,Ho,Wo] float32 or uint16 / int16
+        (its dtype is the output format), or None for the object-owned buffer in out_format (torch.float32, torch.uint16 or
+        torch.int16).  Returns the undistorted frames (0 where a pixel got no depth).  Asynchronous on torch's current stream;
+        no allocation, copy or synchronisation on the device."""
+        if not isinstance(depth, torch.Tensor) or not depth.is_cuda:
+            raise TypeError("depth: expected a CUDA tensor")
+        if depth.dim() != 3 or tuple(depth.shape[1:]) != (self.src_height, self.src_width) or not depth.is_contiguous() or \
+                depth.dtype not in (torch.float32, torch.int16, _U16):
+            raise ValueError(f"depth: expected contiguous float32 / uint16 [n,{self.src_height},{self.src_width}], got "
+                             f"{depth.dtype} {tuple(depth.shape)}")
+        n = depth.shape[0]
+        fmt = _native.KDE_DEPTH_F32 if depth.dtype == torch.float32 else _native.KDE_DEPTH_U16
+        dt = out.dtype if isinstance(out, torch.Tensor) else out_format
+        if dt == torch.float32:
+            ofmt = _native.KDE_DEPTH_F32
+        elif dt is not None and dt in (torch.int16, _U16):
+            ofmt = _native.KDE_DEPTH_U16
+        else:
+            raise ValueError(f"out_format: expected torch.float32 or torch.uint16, got {dt}")
+        if out is not None:
+            _req(out, dt, (n, self.out_height, self.out_width), "out")
+        check(lib().kde_undist_depth_batch(self._h, n, depth.data_ptr(), fmt, ofmt, _ptr(out), _stream()))
+        self._n, self._fmt = n, ofmt
+        return out if out is not None else self.depth_device()
+
+    def depth_device(self) -> torch.Tensor:
+        """the frames of the last depth(): `out` of that call or the object-owned buffer, [n,Ho,Wo] float32, or int16 holding
+        the uint16 bits (`.cpu().numpy().view(numpy.uint16)`)"""
+        p = C.c_void_p()
+        check(lib().kde_undist_depth_device(self._h, C.byref(p)))
+        if self._fmt == _native.KDE_DEPTH_F32:
+            return _view(p.value, (self._n, self.out_height, self.out_width), torch.float32, self)
+        return _view(p.value, (self._n, self.out_height, self.out_width * 2), torch.uint8, self).view(torch.int16)
+
+    def depth_host(self) -> np.ndarray:
+        """the same as a numpy array, float32 or uint16; synchronises torch's current stream"""
+        p = C.c_void_p()
+        check(lib().kde_undist_depth_host(self._h, _stream(), C.byref(p)))
+        ctype, dtype = (C.c_float, np.float32) if self._fmt == _native.KDE_DEPTH_F32 else (C.c_uint16, np.uint16)
+        shape = (self._n, self.out_height, self.out_width)
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(ctype)), shape=shape).astype(dtype, copy=True)
+
+    def filled(self) -> np.ndarray:
+        """the number of output pixels that got a depth per frame of the last depth(), uint32 [n]; synchronises torch's
+        current stream"""
+        p = C.c_void_p()
+        check(lib().kde_undist_filled_host(self._h, _stream(), C.byref(p)))
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint32)), shape=(self._n,)).copy()
+
+    def filled_device(self) -> torch.Tensor:
+        """the same on the device, as raw bytes [n, 4] (uint32), a view of the object-owned buffer"""
+        p = C.c_void_p()
+        check(lib().kde_undist_filled_device(self._h, C.byref(p)))
+        return _view(p.value, (self._n, 4), torch.uint8, self)
+
+    def map(self) -> torch.Tensor:
+        """(us, vs) of every output pixel, float32 [Ho,Wo,2]: the source point it shows, OpenCV's initUndistortRectifyMap
+        product for this calibration.  A view of the object-owned buffer, computed on torch's current stream at the first
+        request after set_calibration()."""
+        p = C.c_void_p()
+        check(lib().kde_undist_map_device(self._h, _stream(), C.byref(p)))
+        return _view(p.value, (self.out_height, self.out_width, 2), torch.float32, self)
+
+
 COMPARE_METHODS = ("input", "jbf", "mrf", "rgbf", "kde")
 
 
