@@ -60,6 +60,24 @@ int kde_test_tree256(const int32_t* iv_rows_dev, const float* fv_rows_dev, uint3
  *             deviation pass and the depth rule (K10); the output must not change by a bit                          */
 int kde_stage_set(float* jbf_avg_dev, float* ers_avg_dev, float* ers_dev_dev, unsigned* counters_dev, int force_full_rules);
 
+/* kde_stage_spdsr_tail(h, n, labels, points, nd_or_null, sweeps, stream) — the tail of kde_spdsr_process_batch (everything
+ * after the back-projection) on the CALLER's labels and cloud instead of the head's, so that a test can feed the plane fit
+ * and the mrf sweeps inputs the segmenters never produce:
+ *   labels_dev  device int32[n*H*W]; any value is tolerated (< 0 or >= rows*cols: the pixel belongs to no cluster)
+ *   points_dev  device kde_float3[n*H*W]
+ *   nd_dev_or_null  NULL: the planes are fitted (launch_spdsr_cluster_planes into the handle's tables, as Process does);
+ *               else device float[n*rows*cols*4], copied into ClusterND_Device INSTEAD of the fit, which makes the
+ *               projection deterministic to the bit
+ *   sweeps      >= 0: number of mrf sweeps (Process always runs 20); 0 leaves optimized = points
+ * Results through the handle's own getters: kde_spdsr_cluster_nd_device, kde_spdsr_plane_fitted_points_device,
+ * kde_spdsr_optimized_points_device / _host (n frames).  h is a kde_spdsr* of THIS library after set_parameters.
+ * Refused with KDE_ERR_INVALID before any launch: a null h / labels / points, SetParametor not called, n outside
+ * 1..max_batch, sweeps < 0.  0 = ok. */
+struct kde_spdsr;
+struct kde_float3;
+int kde_stage_spdsr_tail(struct kde_spdsr* h, int n, const int32_t* labels_dev, const struct kde_float3* points_dev,
+                         const float* nd_dev_or_null, int sweeps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

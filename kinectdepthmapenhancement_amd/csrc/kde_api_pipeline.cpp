@@ -212,6 +212,30 @@ extern "C" int kde_spdsr_process(kde_spdsr* h, const float* depth_dev, const kde
     return kde_spdsr_process_batch(h, 1, depth_dev, points_dev, bgr_dev, stream);
 }
 
+#ifdef KDE_STAGE_HOOKS
+// include/kde_test_hooks.h: exists only in tools/hooks/libkde_hip_stage.so.  What kde_spdsr_process_batch runs after the
+// back-projection, on the caller's labels and cloud (and, if given, the caller's planes instead of the fit).
+extern "C" int kde_stage_spdsr_tail(kde_spdsr* h, int n, const int32_t* labels_dev, const kde_float3* points_dev,
+                                    const float* nd_dev_or_null, int sweeps, void* stream)
+{
+    KDE_REQUIRE(h && labels_dev && points_dev, "kde_stage_spdsr_tail: null argument");
+    KDE_REQUIRE(h->nclusters > 0, "kde_stage_spdsr_tail: SetParametor was not called");
+    KDE_ON_DEVICE(h->p.SP, "kde_stage_spdsr_tail");
+    KDE_REQUIRE(n >= 1 && n <= h->p.max_batch, "kde_stage_spdsr_tail: n=%d outside 1..max_batch=%d", n, h->p.max_batch);
+    KDE_REQUIRE(sweeps >= 0, "kde_stage_spdsr_tail: sweeps=%d is negative", sweeps);
+    hipStream_t s = as_stream(stream);
+    if (nd_dev_or_null)
+        KDE_HIP_TRY(hipMemcpyAsync(h->cluster_nd.p, nd_dev_or_null, (size_t)n * h->nclusters * 4 * sizeof(float),
+                                   hipMemcpyDeviceToDevice, s));
+    else
+        KDE_TRY(launch_spdsr_cluster_planes(h->p.width, h->p.height, n, h->nclusters, h->p.max_batch, labels_dev, points_dev,
+                                            h->sums.p, h->cov.p, h->cluster_nd.p, &h->moments_dirty, s));
+    h->n_last = n;
+    return launch_spdsr_plane_projection(h->p.width, h->p.height, n, h->nclusters, h->cluster_nd.p, labels_dev, points_dev,
+                                         h->nxy.p, h->plane_fitted.p, h->opt_a.p, h->opt_b.p, sweeps, &h->optimized, s);
+}
+#endif
+
 extern "C" int kde_spdsr_refined_depth_device(kde_spdsr* h, float** out)
 {
     KDE_REQUIRE(h, "kde_spdsr_refined_depth_device: null handle");

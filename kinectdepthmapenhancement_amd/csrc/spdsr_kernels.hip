@@ -227,13 +227,17 @@ __global__ __launch_bounds__(kThreads) void set_pseudo_depth_kernel(int npix, in
 // mrf_optimization, Projection_GPU.cu:148-187 with (window 5, K 0.5, smooth_sigma 1.0), D5 (each sweep reads the
 // previous sweep's buffer).  Only the z of a point evolves (x, y = normalized ray * z whenever z is rewritten), so a
 // sweep reads and writes ONE float per pixel instead of two float3 (44 -> 12 B/px): the planes hold z, negated once
-// the pixel has been rewritten at least once (a rewritten z is a weighted mean of values > 50, never 0), and
-// mrf_expand_kernel turns the final plane back into points -- rewritten pixels as ray * z, the others untouched
-// from the input cloud, exactly what 20 in-place float3 sweeps leave behind.
+// the pixel has been rewritten at least once, and mrf_expand_kernel turns the final plane back into points -- rewritten
+// pixels as ray * z, the others untouched from the input cloud, exactly what 20 in-place float3 sweeps leave behind.
+// The mark is the SIGN BIT, not "z < 0": a rewritten z is a weighted mean of values > 50, so never 0 -- but it is NaN once a
+// +inf tap has put inf * 0 into the numerator, -NaN < 0 is false, and the reference leaves that pixel (NaN, NaN, NaN), not
+// the input point.  An unrewritten z carries no sign: z0 is >= +0 and a sweep passes fabsf() of what it read.
 // (Fusing several sweeps per launch through LDS with a halo was measured slower: the sweep is VALU-bound, and the
 // halo recomputation costs more than the saved traffic.  What pays is packed math: a thread owns two horizontally
 // adjacent pixels and every float op of the 25 taps is a v_pk_*_f32 on the pair -- see kde_device_packed.h for the unit
 // geometry -- with the "tap is valid" select folded into a {0, 0.5} factor prepared once per loaded LDS pair.)
+
+__device__ __forceinline__ bool sign_bit(float z) { return (__float_as_uint(z) >> 31) != 0u; }   // true for -NaN as well
 
 constexpr int kSwBX = 32, kSwBY = 8;                  // threads; tile = 64 x 8 pixels
 __global__ __launch_bounds__(kSwBX* kSwBY) void mrf_sweep_kernel(int width, int height, const float* __restrict__ zin,
@@ -268,7 +272,7 @@ __global__ __launch_bounds__(kSwBX* kSwBY) void mrf_sweep_kernel(int width, int 
     __syncthreads();
     if (!own) return;
     f2 oz = {fabsf(zs0), fabsf(zs1)};
-    bool rw0 = zs0 < 0.0f, rw1 = zs1 < 0.0f;
+    bool rw0 = sign_bit(zs0), rw1 = sign_bit(zs1);
     const bool c0 = pf.x > 50.0f && fabsf(oz.x - pf.x) < oz.x * 0.01f;
     const bool c1 = pf.y > 50.0f && fabsf(oz.y - pf.y) < oz.y * 0.01f;
     if (c0 || c1) {
@@ -315,8 +319,8 @@ __global__ __launch_bounds__(kSwBX* kSwBY) void mrf_sweep_kernel(int width, int 
             rw1 = true;
         }
     }
-    zout[p] = rw0 ? -oz.x : oz.x;
-    if (has1) zout[p + 1] = rw1 ? -oz.y : oz.y;
+    zout[p] = rw0 ? -fabsf(oz.x) : oz.x;               // -|z|: the quotient's NaN may carry either sign
+    if (has1) zout[p + 1] = rw1 ? -fabsf(oz.y) : oz.y;
 }
 
 __global__ __launch_bounds__(kThreads) void mrf_expand_kernel(int npix, const float* __restrict__ zfinal,
@@ -331,7 +335,7 @@ __global__ __launch_bounds__(kThreads) void mrf_expand_kernel(int npix, const fl
     }
     const float zs = zfinal[i];
     kde_float3 o = pts[i];
-    if (zs < 0.0f) {
+    if (sign_bit(zs)) {
         const float2 r = nxy[i];
         const float depth = -zs;
         o.z = depth;
