@@ -20,6 +20,7 @@
 //   kde::PointCloudXYZRGB         (extension: the coloured clouds of main.cpp:211-300 for a batch, compacted on the device)
 //   kde::DepthRegistration        (extension: what Kinect.cpp:71-75 asks OpenNI for -- depth warped into the colour camera's view)
 //   kde::LensUndistortion         (extension: frames of a camera with lens distortion resampled into the pinhole view assumed above)
+//   kde::GuidedDepthUpsampling    (extension: low-resolution depth brought to the size of its colour image, guided by that image)
 //
 // What differs from the reference headers, and why:
 //   * cv::gpu::GpuMat parameters are templates over "anything with .data/.rows/.cols/.step" — a real
@@ -1376,6 +1377,76 @@ private:
     static int format(const float*) { return KDE_DEPTH_F32; }
     static int format(const uint16_t*) { return KDE_DEPTH_U16; }
     kde_undist* h_ = nullptr;
+    void* stream_ = nullptr;
+};
+
+// extension (no reference counterpart): a low-resolution depth frame brought to the size of its colour image on the device
+// (kde_upsample_*) by joint bilateral upsampling -- low-resolution samples weighted by a tent of `radius` samples around the
+// output pixel and by the resemblance of the guide colour at the output pixel to the guide colour at the sample -- so that
+// sensors whose depth is smaller than their colour can feed every class above.  The rule is stated in kde_hip.h; with max_gap
+// > 0 no depth is blended across more than max_gap millimetres; deterministic to the bit.  upsample() is asynchronous on the
+// object's stream and capturable; the *_Host members synchronise.
+class GuidedDepthUpsampling {
+public:
+    static kde_upsample_params defaultParams()
+    {
+        kde_upsample_params p{};
+        check(kde_upsample_default_params(&p));
+        return p;
+    }
+    GuidedDepthUpsampling(int src_width, int src_height, int out_width, int out_height, int max_batch = 1)
+    {
+        check(kde_upsample_create(&h_, src_width, src_height, out_width, out_height, max_batch, nullptr));
+    }
+    GuidedDepthUpsampling(int src_width, int src_height, int out_width, int out_height, int max_batch, const kde_upsample_params& params)
+    {
+        check(kde_upsample_create(&h_, src_width, src_height, out_width, out_height, max_batch, &params));
+    }
+    ~GuidedDepthUpsampling() { kde_upsample_destroy(h_); }
+    GuidedDepthUpsampling(const GuidedDepthUpsampling&) = delete;
+    GuidedDepthUpsampling& operator=(const GuidedDepthUpsampling&) = delete;
+
+    // n depth frames back to back, the guide bgr_frames = 1 (one image for every frame) or n images of the output size; the
+    // output format is the type of out_device (nullptr of that type: the object-owned buffer)
+    template <class Depth, class Out>
+    void upsample(int n, const Depth* depth_device, const uint8_t* bgr_device, int bgr_frames, Out* out_device)
+    {
+        check(kde_upsample_depth_batch(h_, n, depth_device, format(depth_device), bgr_device, bgr_frames, format(out_device), out_device,
+                                       stream_));
+    }
+    void* depth_Device() const
+    {
+        void* p = nullptr;
+        check(kde_upsample_depth_device(h_, &p));
+        return p;
+    }
+    const void* depth_Host() const
+    {
+        const void* p = nullptr;
+        check(kde_upsample_depth_host(h_, stream_, &p));
+        return p;
+    }
+    uint32_t* filled_Device() const
+    {
+        uint32_t* p = nullptr;
+        check(kde_upsample_filled_device(h_, &p));
+        return p;
+    }
+    const uint32_t* filled_Host() const
+    {
+        const uint32_t* p = nullptr;
+        check(kde_upsample_filled_host(h_, stream_, &p));
+        return p;
+    }
+    // range[k] for k = |db| + |dg| + |dr| = 0 .. 765, as the kernel reads it
+    void rangeTable(float (&table_host)[766]) const { check(kde_upsample_range_table(h_, table_host, 766)); }
+    void setStream(void* hip_stream) { stream_ = hip_stream; }
+    kde_upsample* handle() const { return h_; }
+
+private:
+    static int format(const float*) { return KDE_DEPTH_F32; }
+    static int format(const uint16_t*) { return KDE_DEPTH_U16; }
+    kde_upsample* h_ = nullptr;
     void* stream_ = nullptr;
 };
 

@@ -819,6 +819,73 @@ int kde_undist_filled_host(kde_undist* h, void* stream, const uint32_t** out);
  * the caller).  The remap calls above compute the map per pixel and do not read it.  No allocation, no synchronisation. */
 int kde_undist_map_device(kde_undist* h, void* stream, const float** out);
 
+/* ==========================================================================================
+ * GuidedDepthUpsampling: a low-resolution depth frame brought to the size of its colour image.  Every class of this library
+ * takes depth and colour of one size; sensors other than a Kinect v1 deliver 512 x 424 or 320 x 240 depth beside 1080p or VGA
+ * colour.  This is joint bilateral upsampling (Kopf et al. 2007): low-resolution samples weighted by their distance to the
+ * output pixel and by how much the full-resolution colour at the output pixel resembles the colour at the sample -- the idea
+ * of JointBilateralFilter on two grids.  A gather, for a batch on the device.  No reference counterpart.
+ *
+ * Frames: depth src_w x src_h (KDE_DEPTH_F32 or KDE_DEPTH_U16, uint16 widened by (float)u), the guide BGR uint8 out_w x out_h,
+ * the output out_w x out_h (either format); out_w >= src_w and out_h >= src_h.  Both images show the same view: pixel centres
+ * at (i + 0.5) / out_w of the width and (qx + 0.5) / src_w of it.
+ *
+ * The rule.  Every operation is one IEEE binary32 operation in the order written, no fused multiply-add, divisions
+ * correctly rounded.  Tables, made once at create on the host:
+ *   sx = (float)src_w / (float)out_w;  sy = (float)src_h / (float)out_h
+ *   gx_of[qx] = clamp((int)rintf(((float)qx + 0.5f) / sx - 0.5f), 0, out_w - 1) for qx = 0 .. src_w - 1, gy_of[qy] likewise:
+ *             the output pixel that "is" low-resolution sample q
+ *   range[k] = (float)exp(-(double)(k * k) / (2.0 * (double)sigma_color * (double)sigma_color)) for k = 0 .. 765
+ * For output pixel (i, j) with guide colour c = bgr(i, j):
+ *   1. u = ((float)i + 0.5f) * sx - 0.5f;  v = ((float)j + 0.5f) * sy - 0.5f;  x0 = floorf(u);  y0 = floorf(v)
+ *   2. taps qy = y0 - r + 1 .. y0 + r (outer loop), qx = x0 - r + 1 .. x0 + r (inner loop), in that order.  A tap outside the
+ *      source frame is absent.  A tap whose depth is not z > z_min && z < z_max is absent (NaN and +-inf fail).
+ *   3. wx = max(1 - fabsf((float)qx - u) / (float)r, 0), wy likewise;  k = |db| + |dg| + |dr| between c and
+ *      bgr(gx_of[qx], gy_of[qy]);  w = (wx * wy) * range[k].  A tap with w == 0 is absent: w > 0 is the test.
+ *   4. max_gap > 0, the guard: zref = the depth of the tap with the largest w, the first such tap in tap order winning a tie;
+ *      taps with fabsf(z - zref) > max_gap are absent.
+ *   5. num = den = 0; per remaining tap in tap order num = num + w * z, den = den + w.  The pixel is num / den, or 0 (the
+ *      sensor's "invalid") if no tap remains.
+ *   6. The output is the float itself (KDE_DEPTH_F32) or depth_to_u16 of it as kde_points_to_depth rounds (KDE_DEPTH_U16).
+ *      filled[f] = the number of pixels of frame f with a remaining tap, counted before the uint16 rounding.
+ * No transcendental is evaluated at run time.  Every output pixel is a function of the source frame, the guide and its own
+ * coordinates, and the count is an integer sum: the result is deterministic to the bit and does not depend on n, a frame's
+ * position in the batch or pointer alignment.
+ * ========================================================================================== */
+typedef struct kde_upsample_params { int radius; float sigma_color; float max_gap; float z_min, z_max; } kde_upsample_params;
+typedef struct kde_upsample kde_upsample;
+/* radius 2, sigma_color 30 (the colour constant of K0, cv_bilateral's, in the same form: an L1 distance, squared), max_gap 0
+ * (no guard), z_min 0, z_max FLT_MAX */
+int kde_upsample_default_params(kde_upsample_params* p);
+/* depth frames of src_w x src_h, guide and output frames of out_w x out_h, max_batch frames on the current device; p == NULL:
+ * the defaults.  KDE_ERR_INVALID: sizes below 1 or a side above 2^24, out_w < src_w or out_h < src_h (this is an upsampler,
+ * and it bounds the taps a tile of output pixels reads), radius outside 1..4, sigma_color not finite or not > 0, max_gap not
+ * finite or < 0, z_min not finite or < 0, z_min >= z_max.  The object owns the tables, filled[max_batch], a count per
+ * workgroup and max_batch * out_w * out_h floats for calls with out_dev == NULL.  On a host without a device the object is
+ * created without buffers: every call validates as usual and the launch then returns KDE_ERR_HIP. */
+int kde_upsample_create(kde_upsample** out, int src_w, int src_h, int out_w, int out_h, int max_batch, const kde_upsample_params* p);
+int kde_upsample_destroy(kde_upsample* h);   /* NULL is a no-op */
+/* n <= max_batch frames: depth_dev is [n][src_h][src_w] of depth_format (KDE_DEPTH_F32 | KDE_DEPTH_U16), bgr_dev is
+ * [bgr_frames][out_h][out_w][3] with bgr_frames == 1 (one guide for every frame) or n, out_dev is [n][out_h][out_w] of
+ * out_format or NULL for the object-owned buffer.  Pointers need the alignment of their element only; output frames on a
+ * 16-byte (float) or 8-byte (uint16) boundary whose width is a multiple of four are written with vector stores, with the same
+ * result.  Two launches: the upsampling, whose workgroups each write their count of filled pixels, and the sum of those
+ * counts into filled[f] -- no atomic, no memset node (kernel nodes keep their order in a replayed graph, a memset node did
+ * not) and nothing to reset; no allocation, no host synchronisation: capturable from the first call. */
+int kde_upsample_depth_batch(kde_upsample* h, int n, const void* depth_dev, int depth_format, const uint8_t* bgr_dev, int bgr_frames,
+                             int out_format, void* out_dev, void* stream);
+/* the frames of the last kde_upsample_depth_batch: out_dev of that call or the object-owned buffer, in that call's
+ * out_format; valid until the next call or destroy.  KDE_ERR_INVALID before the first call. */
+int kde_upsample_depth_device(kde_upsample* h, void** out);
+/* the same in pinned host memory after a blocking copy on `stream`: synchronises; out_dev of the last call must still be alive */
+int kde_upsample_depth_host(kde_upsample* h, void* stream, const void** out);
+int kde_upsample_filled_device(kde_upsample* h, uint32_t** out);   /* filled[n] of the last kde_upsample_depth_batch, on the device */
+/* filled[n] in pinned host memory after a blocking copy on `stream`: synchronises */
+int kde_upsample_filled_host(kde_upsample* h, void* stream, const uint32_t** out);
+/* range[0 .. 765] of the object as the kernel reads it, copied to table_host[capacity]; KDE_ERR_INVALID for capacity < 766.
+ * Host memory only: works without a device. */
+int kde_upsample_range_table(kde_upsample* h, float* table_host, int capacity);
+
 #ifdef __cplusplus
 }
 #endif

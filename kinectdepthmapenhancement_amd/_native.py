@@ -115,6 +115,17 @@ class UndistParams(C.Structure):
     _fields_ = [("z_min", C.c_float), ("z_max", C.c_float), ("depth_interp", C.c_int), ("max_gap", C.c_float)]
 
 
+class UpsampleHandle(C.c_void_p):
+    """kde_upsample*: a ctypes type of its own, like CloudHandle, RegHandle and UndistHandle, which keeps the kde_upsample_*
+    entry points out of the frozen record tools/abi_refusals.py enumerates; tests/test_upsample_abi.py checks their refusals."""
+
+
+class UpsampleParams(C.Structure):
+    """kde_upsample_params (defaults: 2, 30, 0, 0, FLT_MAX -- a 4 x 4 tent, K0's colour constant, no guard, every finite
+    positive depth)."""
+    _fields_ = [("radius", C.c_int), ("sigma_color", C.c_float), ("max_gap", C.c_float), ("z_min", C.c_float), ("z_max", C.c_float)]
+
+
 def build(force: bool = False) -> str:
     """Compile libkde_hip.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     if force:
@@ -315,6 +326,15 @@ SIGNATURES = {
     "kde_undist_filled_device": (_i, [UndistHandle, _pp]),
     "kde_undist_filled_host": (_i, [UndistHandle, _vp, _pp]),
     "kde_undist_map_device": (_i, [UndistHandle, _vp, _pp]),
+    "kde_upsample_default_params": (_i, [C.POINTER(UpsampleParams)]),
+    "kde_upsample_create": (_i, [C.POINTER(UpsampleHandle), _i, _i, _i, _i, _i, C.POINTER(UpsampleParams)]),
+    "kde_upsample_destroy": (_i, [UpsampleHandle]),
+    "kde_upsample_depth_batch": (_i, [UpsampleHandle, _i, _vp, _i, _vp, _i, _i, _vp, _vp]),
+    "kde_upsample_depth_device": (_i, [UpsampleHandle, _pp]),
+    "kde_upsample_depth_host": (_i, [UpsampleHandle, _vp, _pp]),
+    "kde_upsample_filled_device": (_i, [UpsampleHandle, _pp]),
+    "kde_upsample_filled_host": (_i, [UpsampleHandle, _vp, _pp]),
+    "kde_upsample_range_table": (_i, [UpsampleHandle, _vp, _i]),
 }
 
 

@@ -277,6 +277,36 @@ int launch_undist_color(const UndistLaunch& a, const uint8_t* bgr, int bgr_frame
 int launch_undist_depth(const UndistLaunch& a, hipStream_t s);          // 2 kernels: filled = 0, the remap
 int launch_undist_map(const UndistLaunch& a, float2* map, hipStream_t s);   // map [oh][ow] of (us, vs)
 
+// GuidedDepthUpsampling (upsample_kernels.hip): low-resolution depth to the size of its colour image, a gather
+constexpr int kUpsampleRange = 766;                // range[k], k = |db| + |dg| + |dr| = 0 .. 765
+constexpr int kUpsampleMaxRadius = 4;
+constexpr int kUpsampleTileW = 32, kUpsampleTileH = 8;     // output pixels of a tile
+constexpr int kUpsampleTilesPerGroup = 4;          // consecutive tiles (raster order) of one workgroup
+// the tap window of a tile the kernel's LDS arrays hold: the bound derived in upsample_kernels.hip (42 x 18) and two to spare
+constexpr int kUpsampleWinW = kUpsampleTileW + 2 * kUpsampleMaxRadius + 4, kUpsampleWinH = kUpsampleTileH + 2 * kUpsampleMaxRadius + 4;
+// x0 of output column i (y0 of row j with sy): one function for the kernel and for the window check of kde_upsample_create
+__host__ __device__ inline int upsample_floor(int i, float scale) { return (int)floorf(((float)i + 0.5f) * scale - 0.5f); }
+struct UpsampleLaunch {
+    int n;
+    int sw, sh, ow, oh;                            // source and output frame
+    int radius;                                    // 1 .. kUpsampleMaxRadius
+    float sx, sy;                                  // (float)sw / (float)ow, (float)sh / (float)oh
+    float max_gap, z_min, z_max;                   // max_gap 0: no guard
+    const void* depth;                             // [n][sh][sw] float or uint16
+    int depth_format;                              // KDE_DEPTH_*
+    const uint8_t* bgr;                            // [bgr_frames][oh][ow][3]
+    int bgr_frames;                                // 1 or n
+    void* out;                                     // [n][oh][ow] float or uint16
+    int out_format;                                // KDE_DEPTH_*
+    const int* gx_of;                              // [sw]: the output column that is source column qx
+    const int* gy_of;                              // [sh]
+    const float* range;                            // [kUpsampleRange]
+    uint32_t* partial;                             // [n][upsample_groups(ow, oh)]: the count of each workgroup
+    uint32_t* filled;                              // [n]
+};
+unsigned upsample_groups(int ow, int oh);                     // workgroups per frame
+int launch_upsample(const UpsampleLaunch& a, hipStream_t s);  // 2 kernels: the upsampling, filled = the sum of its counts
+
 struct DaspGeom {
     int width, height, rows, cols, wx, wy;
 };

@@ -1187,6 +1187,99 @@ class LensUndistortion(_Handle):
         return _view(p.value, (self.out_height, self.out_width, 2), torch.float32, self)
 
 
+class GuidedDepthUpsampling(_Handle):
+    """A low-resolution depth frame brought to the size of its colour image on the device (kde_upsample_*): joint bilateral
+    upsampling, low-resolution samples weighted by a tent of radius `radius` around the output pixel and by the resemblance
+    of the guide colour at the output pixel to the guide colour at the sample.  src_size and out_size are (width, height),
+    out_size no smaller than src_size; params is an UpsampleParams (radius, sigma_color, max_gap, z_min, z_max) or None for the
+    defaults (2, 30, no guard, every finite positive depth).  The rule is stated in include/kde_hip.h; deterministic to the
+    bit."""
+    _destroy = "kde_upsample_destroy"
+    _handle_type = _native.UpsampleHandle
+
+    def __init__(self, src_size, out_size, max_batch: int = 1, params: Optional["_native.UpsampleParams"] = None):
+        super().__init__()
+        self.src_width, self.src_height = src_size
+        self.out_width, self.out_height = out_size
+        self.max_batch = max_batch
+        self._n, self._fmt = 0, _native.KDE_DEPTH_F32
+        check(lib().kde_upsample_create(C.byref(self._h), self.src_width, self.src_height, self.out_width, self.out_height,
+                                        max_batch, None if params is None else C.byref(params)))
+
+    @staticmethod
+    def default_params() -> "_native.UpsampleParams":
+        p = _native.UpsampleParams()
+        check(lib().kde_upsample_default_params(C.byref(p)))
+        return p
+
+    def range_table(self) -> np.ndarray:
+        """range[k] for k = |db| + |dg| + |dr| = 0 .. 765 as the kernel reads it, float32 [766]; needs no device"""
+        t = np.empty(766, np.float32)
+        check(lib().kde_upsample_range_table(self._h, t.ctypes.data, t.size))
+        return t
+
+    def upsample(self, depth: torch.Tensor, bgr: torch.Tensor, out: Optional[torch.Tensor] = None,
+                 out_format=torch.float32) -> torch.Tensor:
+        """depth: [n,Hs,Ws] float32, or uint16 / int16 holding the sensor's uint16.  bgr: the guide, uint8 [n,Ho,Wo,3], or
+        [1,Ho,Wo,3] for one guide for every frame.  out: [n,Ho,Wo] float32 or uint16 / int16 (its dtype is the output
+        format), or None for the object-owned buffer in out_format (torch.float32, torch.uint16 or torch.int16).  Returns
+        the upsampled frames (0 where a pixel got no depth).  Asynchronous on torch's current stream; no allocation, copy
+        or synchronisation on the device."""
+        if not isinstance(depth, torch.Tensor) or not depth.is_cuda:
+            raise TypeError("depth: expected a CUDA tensor")
+        if depth.dim() != 3 or tuple(depth.shape[1:]) != (self.src_height, self.src_width) or not depth.is_contiguous() or \
+                depth.dtype not in (torch.float32, torch.int16, _U16):
+            raise ValueError(f"depth: expected contiguous float32 / uint16 [n,{self.src_height},{self.src_width}], got "
+                             f"{depth.dtype} {tuple(depth.shape)}")
+        n = depth.shape[0]
+        if not isinstance(bgr, torch.Tensor) or bgr.dim() != 4 or bgr.shape[0] not in (1, n):
+            raise ValueError(f"bgr: expected [1 or {n},{self.out_height},{self.out_width},3] uint8")
+        _req(bgr, torch.uint8, (bgr.shape[0], self.out_height, self.out_width, 3), "bgr")
+        fmt = _native.KDE_DEPTH_F32 if depth.dtype == torch.float32 else _native.KDE_DEPTH_U16
+        dt = out.dtype if isinstance(out, torch.Tensor) else out_format
+        if dt == torch.float32:
+            ofmt = _native.KDE_DEPTH_F32
+        elif dt is not None and dt in (torch.int16, _U16):
+            ofmt = _native.KDE_DEPTH_U16
+        else:
+            raise ValueError(f"out_format: expected torch.float32 or torch.uint16, got {dt}")
+        if out is not None:
+            _req(out, dt, (n, self.out_height, self.out_width), "out")
+        check(lib().kde_upsample_depth_batch(self._h, n, depth.data_ptr(), fmt, bgr.data_ptr(), bgr.shape[0], ofmt, _ptr(out), _stream()))
+        self._n, self._fmt = n, ofmt
+        return out if out is not None else self.depth_device()
+
+    def depth_device(self) -> torch.Tensor:
+        """the frames of the last upsample(): `out` of that call or the object-owned buffer, [n,Ho,Wo] float32, or int16
+        holding the uint16 bits (`.cpu().numpy().view(numpy.uint16)`)"""
+        p = C.c_void_p()
+        check(lib().kde_upsample_depth_device(self._h, C.byref(p)))
+        if self._fmt == _native.KDE_DEPTH_F32:
+            return _view(p.value, (self._n, self.out_height, self.out_width), torch.float32, self)
+        return _view(p.value, (self._n, self.out_height, self.out_width * 2), torch.uint8, self).view(torch.int16)
+
+    def depth_host(self) -> np.ndarray:
+        """the same as a numpy array, float32 or uint16; synchronises torch's current stream"""
+        p = C.c_void_p()
+        check(lib().kde_upsample_depth_host(self._h, _stream(), C.byref(p)))
+        ctype, dtype = (C.c_float, np.float32) if self._fmt == _native.KDE_DEPTH_F32 else (C.c_uint16, np.uint16)
+        shape = (self._n, self.out_height, self.out_width)
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(ctype)), shape=shape).astype(dtype, copy=True)
+
+    def filled(self) -> np.ndarray:
+        """the number of output pixels that got a depth per frame of the last upsample(), uint32 [n]; synchronises torch's
+        current stream"""
+        p = C.c_void_p()
+        check(lib().kde_upsample_filled_host(self._h, _stream(), C.byref(p)))
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint32)), shape=(self._n,)).copy()
+
+    def filled_device(self) -> torch.Tensor:
+        """the same on the device, as raw bytes [n, 4] (uint32), a view of the object-owned buffer"""
+        p = C.c_void_p()
+        check(lib().kde_upsample_filled_device(self._h, C.byref(p)))
+        return _view(p.value, (self._n, 4), torch.uint8, self)
+
+
 COMPARE_METHODS = ("input", "jbf", "mrf", "rgbf", "kde")
 
 
