@@ -1450,6 +1450,95 @@ private:
     void* stream_ = nullptr;
 };
 
+// extension (no reference counterpart): the holes of a depth frame filled on the device under the guide of its colour image
+// (kde_holefill_*) -- `iterations` passes, each of which gives the hole pixels with at least `min_taps` usable neighbours within
+// `radius` the mean of those neighbours, weighted by distance and by the resemblance of the guide colour -- behind the
+// registration, the undistortion and the upsampling, which leave holes, and in front of the filters, which reach two or three
+// pixels into one.  iterations * radius bounds how far a fill reaches.  The rule is stated in kde_hip.h; with max_gap > 0 no
+// depth is blended across more than max_gap millimetres; deterministic to the bit.  fill() is asynchronous on the object's
+// stream and capturable; the *_Host members synchronise.
+class DepthHoleFilling {
+public:
+    static kde_holefill_params defaultParams()
+    {
+        kde_holefill_params p{};
+        check(kde_holefill_default_params(&p));
+        return p;
+    }
+    DepthHoleFilling(int width, int height, int max_batch = 1) { check(kde_holefill_create(&h_, width, height, max_batch, nullptr)); }
+    DepthHoleFilling(int width, int height, int max_batch, const kde_holefill_params& params)
+    {
+        check(kde_holefill_create(&h_, width, height, max_batch, &params));
+    }
+    ~DepthHoleFilling() { kde_holefill_destroy(h_); }
+    DepthHoleFilling(const DepthHoleFilling&) = delete;
+    DepthHoleFilling& operator=(const DepthHoleFilling&) = delete;
+
+    // n depth frames back to back, the guide bgr_frames = 1 (one image for every frame) or n images; the output format is the
+    // type of out_device (nullptr of that type: the object-owned buffer), which must not overlap depth_device; pass_of_device:
+    // n frames of uint8 (0 original, p filled in pass p, 255 still a hole) or nullptr where it is not wanted
+    template <class Depth, class Out>
+    void fill(int n, const Depth* depth_device, const uint8_t* bgr_device, int bgr_frames, Out* out_device, uint8_t* pass_of_device = nullptr)
+    {
+        check(kde_holefill_fill_batch(h_, n, depth_device, format(depth_device), bgr_device, bgr_frames, format(out_device), out_device,
+                                      pass_of_device, stream_));
+    }
+    void* depth_Device() const
+    {
+        void* p = nullptr;
+        check(kde_holefill_depth_device(h_, &p));
+        return p;
+    }
+    const void* depth_Host() const
+    {
+        const void* p = nullptr;
+        check(kde_holefill_depth_host(h_, stream_, &p));
+        return p;
+    }
+    uint32_t* filled_Device() const
+    {
+        uint32_t* p = nullptr;
+        check(kde_holefill_filled_device(h_, &p));
+        return p;
+    }
+    const uint32_t* filled_Host() const
+    {
+        const uint32_t* p = nullptr;
+        check(kde_holefill_filled_host(h_, stream_, &p));
+        return p;
+    }
+    uint32_t* remaining_Device() const
+    {
+        uint32_t* p = nullptr;
+        check(kde_holefill_remaining_device(h_, &p));
+        return p;
+    }
+    const uint32_t* remaining_Host() const
+    {
+        const uint32_t* p = nullptr;
+        check(kde_holefill_remaining_host(h_, stream_, &p));
+        return p;
+    }
+    // the number of passes one launch performs
+    int passesPerLaunch() const
+    {
+        int k = 0;
+        check(kde_holefill_passes_per_launch(h_, &k));
+        return k;
+    }
+    // space[(2 radius + 1)^2] (capacity: the entries table_host holds) and range[k] for k = |db| + |dg| + |dr| = 0 .. 765
+    void spaceTable(float* table_host, int capacity) const { check(kde_holefill_space_table(h_, table_host, capacity)); }
+    void rangeTable(float (&table_host)[766]) const { check(kde_holefill_range_table(h_, table_host, 766)); }
+    void setStream(void* hip_stream) { stream_ = hip_stream; }
+    kde_holefill* handle() const { return h_; }
+
+private:
+    static int format(const float*) { return KDE_DEPTH_F32; }
+    static int format(const uint16_t*) { return KDE_DEPTH_U16; }
+    kde_holefill* h_ = nullptr;
+    void* stream_ = nullptr;
+};
+
 }  // namespace kde
 
 #ifndef KDE_NO_GLOBAL_NAMES

@@ -886,6 +886,94 @@ int kde_upsample_filled_host(kde_upsample* h, void* stream, const uint32_t** out
  * Host memory only: works without a device. */
 int kde_upsample_range_table(kde_upsample* h, float* table_host, int capacity);
 
+/* ==========================================================================================
+ * DepthHoleFilling: the holes of a depth frame filled from their valid neighbours under the guide of its colour image.  The
+ * registration's z-buffer leaves occlusion bands and cracks, the undistortion an invalid rim, a Kinect a shadow band beside
+ * every foreground object, a time-of-flight sensor drops dark surfaces; the filters behind reach two or three pixels into a
+ * hole.  This stage closes a hole front by front: each pass fills the hole pixels that have enough valid neighbours within
+ * `radius`, from those neighbours, weighted by distance and by how much the guide colour at the neighbour resembles the
+ * colour at the pixel; the next pass builds on the result.  iterations * radius bounds how far a fill reaches.  For a batch on
+ * the device.  No reference counterpart.
+ *
+ * Frames: depth width x height (KDE_DEPTH_F32 or KDE_DEPTH_U16, uint16 widened by (float)u), the guide BGR uint8 and the
+ * output (either format) of the same size.
+ *
+ * The rule.  Every operation is one IEEE binary32 operation in the order written, no fused multiply-add, divisions
+ * correctly rounded.  With r = radius and N = iterations.  Tables, made once at create on the host:
+ *   space[dy + r][dx + r] = (float)exp(-(double)(dx * dx + dy * dy) / (2.0 * (double)sigma_space * (double)sigma_space))
+ *   range[k] = (float)exp(-(double)(k * k) / (2.0 * (double)sigma_color * (double)sigma_color)) for k = 0 .. 765
+ * The state of a frame is a float image z in which 0 means "hole".
+ *   Pass 0 sanitises the input: z = (d > z_min && d < z_max) ? (float)d : 0 (NaN and +-inf become holes); pass_of = 0 where
+ *   z > 0 and 255 elsewhere.
+ *   Pass p = 1 .. N reads the state of pass p - 1 as a snapshot and writes a new state.  For each pixel with z == 0:
+ *   1. its taps are dy = -r .. r (outer loop), dx = -r .. r (inner loop), without the centre, in that order.
+ *   2. A tap is absent if it lies outside the frame or has z == 0.
+ *   3. k = |db| + |dg| + |dr| between the guide at the pixel and the guide at the tap.
+ *   4. w = space[dy + r][dx + r] * range[k].  A tap with w == 0 is absent: w > 0 is the test.
+ *   5. support = the number of taps that remain.
+ *   6. max_gap > 0, the guard: zref = the depth of the heaviest remaining tap, the first such tap in tap order winning a tie
+ *      (gap_rule 0), or the largest depth among the remaining taps -- the background, where a shadow band belongs (gap_rule
+ *      1); taps with fabsf(z - zref) > max_gap become absent.  support is not recounted.
+ *   7. num = den = 0; per remaining tap in tap order num = num + w * z, den = den + w;  v = num / den.
+ *   8. The pixel becomes v with pass_of = p iff support >= min_taps and v > 0; otherwise it stays 0.
+ *   Pixels with z > 0 never change, in any pass.
+ * After pass N, per frame: the output is the state itself (KDE_DEPTH_F32) or depth_to_u16 of it as kde_points_to_depth rounds
+ * (KDE_DEPTH_U16); filled[f] = the number of pixels with 1 <= pass_of <= N, remaining[f] = the number still 0, both counted
+ * before the uint16 rounding; pass_of is 0 for an original pixel, p for one filled in pass p, 255 for one that is still a hole.
+ * N passes and then M more on the float result equal N + M passes (at the default z_min and z_max): validity is z > 0 on the
+ * state and nothing else.  A fill from equal depths need not be that depth to the bit: num / den rounds.
+ * No transcendental is evaluated at run time.  Every pixel of a pass is a function of the snapshot before it, the guide and
+ * the tables, and the counts are integer sums: the result is deterministic to the bit and does not depend on n, a frame's
+ * position in the batch, pointer alignment or passes_per_launch.
+ * ========================================================================================== */
+typedef struct kde_holefill_params { int radius; int iterations; int min_taps; float sigma_space; float sigma_color;
+                                     float max_gap; int gap_rule; float z_min, z_max; int passes_per_launch; } kde_holefill_params;
+typedef struct kde_holefill kde_holefill;
+/* radius 2, iterations 8, min_taps 3, sigma_space 2, sigma_color 30 (the colour constant of K0, in the same form: an L1
+ * distance, squared), max_gap 0 (no guard), gap_rule 0 (heaviest; 1: farthest), z_min 0, z_max FLT_MAX, passes_per_launch 0
+ * (the library's choice for the radius and the guard; 1 .. 4: forced) */
+int kde_holefill_default_params(kde_holefill_params* p);
+/* frames of width x height, max_batch of them on the current device; p == NULL: the defaults.  KDE_ERR_INVALID: sizes below 1
+ * or a side above 2^24, radius outside 1..3, iterations outside 1..64, min_taps outside 1..(2 radius + 1)^2 - 1, sigma_space or
+ * sigma_color not finite or not > 0, max_gap not finite or < 0, gap_rule neither 0 nor 1, z_min not finite or < 0, z_min >=
+ * z_max, passes_per_launch outside 0..4.  The object owns the tables, the two counts per frame and per workgroup, pass_of for
+ * calls without pass_of_dev, max_batch * width * height floats for calls with out_dev == NULL and up to two more such images
+ * for the state between launches.  On a host without a device the object is created without buffers: every call validates as
+ * usual and the launch then returns KDE_ERR_HIP. */
+int kde_holefill_create(kde_holefill** out, int width, int height, int max_batch, const kde_holefill_params* p);
+int kde_holefill_destroy(kde_holefill* h);   /* NULL is a no-op */
+/* n <= max_batch frames: depth_dev is [n][height][width] of depth_format (KDE_DEPTH_F32 | KDE_DEPTH_U16), bgr_dev is
+ * [bgr_frames][height][width][3] with bgr_frames == 1 (one guide for every frame) or n, out_dev is [n][height][width] of
+ * out_format or NULL for the object-owned buffer, pass_of_dev is [n][height][width] uint8 or NULL where it is not wanted.
+ * Pointers need the alignment of their element only.  In place is refused: KDE_ERR_INVALID where the frames that are written
+ * -- out_dev's, or with out_dev == NULL the object-owned buffer's, which kde_holefill_depth_device hands out -- overlap those
+ * of depth_dev (a workgroup reads the neighbourhood of its tile while its neighbours write theirs).  To run more passes on a
+ * result, pass a buffer for the new result.
+ * One launch performs k = passes_per_launch passes in on-chip memory, on a tile and a halo of k * radius pixels around it, so
+ * the N passes take ceil(N / k) launches between two object-owned state images, the last of which converts to out_format and
+ * writes each workgroup's two counts; one more launch sums them into filled[f] and remaining[f] -- no atomic, no memset node
+ * (kernel nodes keep their order in a replayed graph, a memset node did not) and nothing to reset; no allocation, no host
+ * synchronisation: capturable from the first call.  A tile without a hole does no pass and only moves its bytes. */
+int kde_holefill_fill_batch(kde_holefill* h, int n, const void* depth_dev, int depth_format, const uint8_t* bgr_dev, int bgr_frames,
+                            int out_format, void* out_dev, uint8_t* pass_of_dev /* NULL: not wanted */, void* stream);
+/* the frames of the last kde_holefill_fill_batch: out_dev of that call or the object-owned buffer, in that call's out_format;
+ * valid until the next call or destroy.  KDE_ERR_INVALID before the first call (this and the five getters below). */
+int kde_holefill_depth_device(kde_holefill* h, void** out);
+/* the same in pinned host memory after a blocking copy on `stream`: synchronises; out_dev of the last call must still be alive */
+int kde_holefill_depth_host(kde_holefill* h, void* stream, const void** out);
+int kde_holefill_filled_device(kde_holefill* h, uint32_t** out);   /* filled[n] of the last kde_holefill_fill_batch, on the device */
+/* filled[n] in pinned host memory after a blocking copy on `stream`: synchronises */
+int kde_holefill_filled_host(kde_holefill* h, void* stream, const uint32_t** out);
+int kde_holefill_remaining_device(kde_holefill* h, uint32_t** out);   /* remaining[n] of the last call, on the device */
+int kde_holefill_remaining_host(kde_holefill* h, void* stream, const uint32_t** out);   /* synchronises */
+/* the k the object runs with: passes_per_launch where it was given, the library's choice where it was 0 (4, 2, 2 for radius
+ * 1, 2, 3; 1 for radius 3 with the guard) */
+int kde_holefill_passes_per_launch(kde_holefill* h, int* out);
+/* space[(2 radius + 1)^2] (row dy + r, column dx + r) and range[0 .. 765] of the object as the kernel reads them, copied to
+ * table_host[capacity]; KDE_ERR_INVALID for a capacity below the table's size.  Host memory only: work without a device. */
+int kde_holefill_space_table(kde_holefill* h, float* table_host, int capacity);
+int kde_holefill_range_table(kde_holefill* h, float* table_host, int capacity);
+
 #ifdef __cplusplus
 }
 #endif

@@ -126,6 +126,20 @@ class UpsampleParams(C.Structure):
     _fields_ = [("radius", C.c_int), ("sigma_color", C.c_float), ("max_gap", C.c_float), ("z_min", C.c_float), ("z_max", C.c_float)]
 
 
+class HolefillHandle(C.c_void_p):
+    """kde_holefill*: a ctypes type of its own, like CloudHandle, RegHandle, UndistHandle and UpsampleHandle, which keeps the
+    kde_holefill_* entry points out of the frozen record tools/abi_refusals.py enumerates; tests/test_holefill_abi.py checks
+    their refusals."""
+
+
+class HolefillParams(C.Structure):
+    """kde_holefill_params (defaults: 2, 8, 3, 2, 30, 0, 0, 0, FLT_MAX, 0 -- a 5 x 5 window, 8 passes, 3 taps, K0's colour
+    constant, no guard, every finite positive depth, the library's passes per launch)."""
+    _fields_ = [("radius", C.c_int), ("iterations", C.c_int), ("min_taps", C.c_int), ("sigma_space", C.c_float),
+                ("sigma_color", C.c_float), ("max_gap", C.c_float), ("gap_rule", C.c_int), ("z_min", C.c_float), ("z_max", C.c_float),
+                ("passes_per_launch", C.c_int)]
+
+
 def build(force: bool = False) -> str:
     """Compile libkde_hip.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     if force:
@@ -335,6 +349,19 @@ SIGNATURES = {
     "kde_upsample_filled_device": (_i, [UpsampleHandle, _pp]),
     "kde_upsample_filled_host": (_i, [UpsampleHandle, _vp, _pp]),
     "kde_upsample_range_table": (_i, [UpsampleHandle, _vp, _i]),
+    "kde_holefill_default_params": (_i, [C.POINTER(HolefillParams)]),
+    "kde_holefill_create": (_i, [C.POINTER(HolefillHandle), _i, _i, _i, C.POINTER(HolefillParams)]),
+    "kde_holefill_destroy": (_i, [HolefillHandle]),
+    "kde_holefill_fill_batch": (_i, [HolefillHandle, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp]),
+    "kde_holefill_depth_device": (_i, [HolefillHandle, _pp]),
+    "kde_holefill_depth_host": (_i, [HolefillHandle, _vp, _pp]),
+    "kde_holefill_filled_device": (_i, [HolefillHandle, _pp]),
+    "kde_holefill_filled_host": (_i, [HolefillHandle, _vp, _pp]),
+    "kde_holefill_remaining_device": (_i, [HolefillHandle, _pp]),
+    "kde_holefill_remaining_host": (_i, [HolefillHandle, _vp, _pp]),
+    "kde_holefill_passes_per_launch": (_i, [HolefillHandle, C.POINTER(_i)]),
+    "kde_holefill_space_table": (_i, [HolefillHandle, _vp, _i]),
+    "kde_holefill_range_table": (_i, [HolefillHandle, _vp, _i]),
 }
 
 

@@ -307,6 +307,45 @@ struct UpsampleLaunch {
 unsigned upsample_groups(int ow, int oh);                     // workgroups per frame
 int launch_upsample(const UpsampleLaunch& a, hipStream_t s);  // 2 kernels: the upsampling, filled = the sum of its counts
 
+// DepthHoleFilling (holefill_kernels.hip): holes filled from their valid neighbours under a colour guide, pass by pass
+constexpr int kHolefillRange = 766;                // range[k], k = |db| + |dg| + |dr| = 0 .. 765
+constexpr int kHolefillMaxRadius = 3;
+constexpr int kHolefillMaxIterations = 64;
+constexpr int kHolefillMaxFuse = 4;                // passes one launch performs in LDS, at the most
+constexpr int kHolefillTileW = 32, kHolefillTileH = 16;    // pixels of a workgroup's tile
+struct HolefillLaunch {
+    int n;
+    int w, h;
+    int radius;                                    // 1 .. kHolefillMaxRadius
+    int iterations;                                // 1 .. kHolefillMaxIterations
+    int fuse;                                      // 1 .. kHolefillMaxFuse passes per launch
+    int min_taps, gap_rule;
+    float max_gap, z_min, z_max;                   // max_gap 0: no guard
+    const void* depth;                             // [n][h][w] float or uint16
+    int depth_format;                              // KDE_DEPTH_*
+    const uint8_t* bgr;                            // [bgr_frames][h][w][3]
+    int bgr_frames;                                // 1 or n
+    void* out;                                     // [n][h][w] float or uint16; overlaps neither depth nor state
+    int out_format;                                // KDE_DEPTH_*
+    float* state[2];                               // [n][h][w] each: the state between two launches
+    uint8_t* pass;                                 // [n][h][w]: pass_of, in place between launches and the result
+    const float* space;                            // [(2 radius + 1)^2]
+    const float* range;                            // [kHolefillRange]
+    uint32_t* partial;                             // [n][holefill_groups(w, h)][2]: the two counts of each workgroup
+    uint32_t* filled;                              // [n]
+    uint32_t* remaining;                           // [n]
+    // one launch of the fill kernel (set by launch_holefill)
+    const void* src;                               // the state it reads: depth, or what the launch before it wrote
+    int src_format;
+    void* dst;
+    int dst_format;
+    int p0, passes;                                // it performs passes p0 + 1 .. p0 + passes
+    bool first, last;                              // first: src is the caller's depth and is sanitised; last: dst is out, counts
+};
+unsigned holefill_groups(int w, int h);                       // workgroups per frame
+// ceil(iterations / fuse) launches of the fill kernel, then filled / remaining = the sums of the last one's counts
+int launch_holefill(const HolefillLaunch& a, hipStream_t s);
+
 struct DaspGeom {
     int width, height, rows, cols, wx, wy;
 };

@@ -1280,6 +1280,127 @@ class GuidedDepthUpsampling(_Handle):
         return _view(p.value, (self._n, 4), torch.uint8, self)
 
 
+class DepthHoleFilling(_Handle):
+    """The holes of a depth frame filled on the device under the guide of its colour image (kde_holefill_*): `iterations`
+    passes, each of which gives the hole pixels with at least `min_taps` usable neighbours within `radius` the mean of those
+    neighbours, weighted by distance and by the resemblance of the guide colour; iterations * radius bounds how far a fill
+    reaches.  size is (width, height); params is a HolefillParams (radius, iterations, min_taps, sigma_space, sigma_color,
+    max_gap, gap_rule, z_min, z_max, passes_per_launch) or None for the defaults (2, 8, 3, 2, 30, no guard, every finite
+    positive depth, the library's passes per launch).  The rule is stated in include/kde_hip.h; deterministic to the bit."""
+    _destroy = "kde_holefill_destroy"
+    _handle_type = _native.HolefillHandle
+
+    def __init__(self, size, max_batch: int = 1, params: Optional["_native.HolefillParams"] = None):
+        super().__init__()
+        self.width, self.height = size
+        self.max_batch = max_batch
+        self._n, self._fmt = 0, _native.KDE_DEPTH_F32
+        check(lib().kde_holefill_create(C.byref(self._h), self.width, self.height, max_batch, None if params is None else C.byref(params)))
+        self.radius = (self.default_params() if params is None else params).radius
+
+    @staticmethod
+    def default_params() -> "_native.HolefillParams":
+        p = _native.HolefillParams()
+        check(lib().kde_holefill_default_params(C.byref(p)))
+        return p
+
+    def space_table(self) -> np.ndarray:
+        """space[dy + r][dx + r] as the kernel reads it, float32 [2r + 1, 2r + 1]; needs no device"""
+        side = 2 * self.radius + 1
+        t = np.empty((side, side), np.float32)
+        check(lib().kde_holefill_space_table(self._h, t.ctypes.data, t.size))
+        return t
+
+    def range_table(self) -> np.ndarray:
+        """range[k] for k = |db| + |dg| + |dr| = 0 .. 765 as the kernel reads it, float32 [766]; needs no device"""
+        t = np.empty(766, np.float32)
+        check(lib().kde_holefill_range_table(self._h, t.ctypes.data, t.size))
+        return t
+
+    def passes_per_launch(self) -> int:
+        """the number of passes one launch performs: passes_per_launch of the parameters, or the library's choice"""
+        k = C.c_int()
+        check(lib().kde_holefill_passes_per_launch(self._h, C.byref(k)))
+        return k.value
+
+    def fill(self, depth: torch.Tensor, bgr: torch.Tensor, out: Optional[torch.Tensor] = None, out_format=torch.float32,
+             pass_of: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """depth: [n,H,W] float32, or uint16 / int16 holding the sensor's uint16.  bgr: the guide, uint8 [n,H,W,3], or
+        [1,H,W,3] for one guide for every frame.  out: [n,H,W] float32 or uint16 / int16 (its dtype is the output format),
+        or None for the object-owned buffer in out_format (torch.float32, torch.uint16 or torch.int16); what is written
+        must not overlap depth, so a result returned by fill(..., out=None) goes back in only with an `out` for the new one.  pass_of: uint8 [n,H,W] or None: 0 for an original pixel, p for one filled in pass p, 255 for one that is
+        still a hole.  Returns the filled frames (0 where a hole remains).  Asynchronous on torch's current stream; no
+        allocation, copy or synchronisation on the device."""
+        if not isinstance(depth, torch.Tensor) or not depth.is_cuda:
+            raise TypeError("depth: expected a CUDA tensor")
+        if depth.dim() != 3 or tuple(depth.shape[1:]) != (self.height, self.width) or not depth.is_contiguous() or \
+                depth.dtype not in (torch.float32, torch.int16, _U16):
+            raise ValueError(f"depth: expected contiguous float32 / uint16 [n,{self.height},{self.width}], got "
+                             f"{depth.dtype} {tuple(depth.shape)}")
+        n = depth.shape[0]
+        if not isinstance(bgr, torch.Tensor) or bgr.dim() != 4 or bgr.shape[0] not in (1, n):
+            raise ValueError(f"bgr: expected [1 or {n},{self.height},{self.width},3] uint8")
+        _req(bgr, torch.uint8, (bgr.shape[0], self.height, self.width, 3), "bgr")
+        fmt = _native.KDE_DEPTH_F32 if depth.dtype == torch.float32 else _native.KDE_DEPTH_U16
+        dt = out.dtype if isinstance(out, torch.Tensor) else out_format
+        if dt == torch.float32:
+            ofmt = _native.KDE_DEPTH_F32
+        elif dt is not None and dt in (torch.int16, _U16):
+            ofmt = _native.KDE_DEPTH_U16
+        else:
+            raise ValueError(f"out_format: expected torch.float32 or torch.uint16, got {dt}")
+        if out is not None:
+            _req(out, dt, (n, self.height, self.width), "out")
+        if pass_of is not None:
+            _req(pass_of, torch.uint8, (n, self.height, self.width), "pass_of")
+        check(lib().kde_holefill_fill_batch(self._h, n, depth.data_ptr(), fmt, bgr.data_ptr(), bgr.shape[0], ofmt, _ptr(out), _ptr(pass_of),
+                                            _stream()))
+        self._n, self._fmt = n, ofmt
+        return out if out is not None else self.depth_device()
+
+    def depth_device(self) -> torch.Tensor:
+        """the frames of the last fill(): `out` of that call or the object-owned buffer, [n,H,W] float32, or int16 holding
+        the uint16 bits (`.cpu().numpy().view(numpy.uint16)`)"""
+        p = C.c_void_p()
+        check(lib().kde_holefill_depth_device(self._h, C.byref(p)))
+        if self._fmt == _native.KDE_DEPTH_F32:
+            return _view(p.value, (self._n, self.height, self.width), torch.float32, self)
+        return _view(p.value, (self._n, self.height, self.width * 2), torch.uint8, self).view(torch.int16)
+
+    def depth_host(self) -> np.ndarray:
+        """the same as a numpy array, float32 or uint16; synchronises torch's current stream"""
+        p = C.c_void_p()
+        check(lib().kde_holefill_depth_host(self._h, _stream(), C.byref(p)))
+        ctype, dtype = (C.c_float, np.float32) if self._fmt == _native.KDE_DEPTH_F32 else (C.c_uint16, np.uint16)
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(ctype)), shape=(self._n, self.height, self.width)).astype(dtype, copy=True)
+
+    def _count_host(self, fn) -> np.ndarray:
+        p = C.c_void_p()
+        check(fn(self._h, _stream(), C.byref(p)))
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint32)), shape=(self._n,)).copy()
+
+    def _count_device(self, fn) -> torch.Tensor:
+        p = C.c_void_p()
+        check(fn(self._h, C.byref(p)))
+        return _view(p.value, (self._n, 4), torch.uint8, self)
+
+    def filled(self) -> np.ndarray:
+        """the number of pixels per frame the last fill() gave a depth, uint32 [n]; synchronises torch's current stream"""
+        return self._count_host(lib().kde_holefill_filled_host)
+
+    def remaining(self) -> np.ndarray:
+        """the number of pixels per frame that are still holes after the last fill(), uint32 [n]; synchronises"""
+        return self._count_host(lib().kde_holefill_remaining_host)
+
+    def filled_device(self) -> torch.Tensor:
+        """filled on the device, as raw bytes [n, 4] (uint32), a view of the object-owned buffer"""
+        return self._count_device(lib().kde_holefill_filled_device)
+
+    def remaining_device(self) -> torch.Tensor:
+        """remaining on the device, as raw bytes [n, 4] (uint32), a view of the object-owned buffer"""
+        return self._count_device(lib().kde_holefill_remaining_device)
+
+
 COMPARE_METHODS = ("input", "jbf", "mrf", "rgbf", "kde")
 
 
