@@ -1205,19 +1205,71 @@ private:
     void* stream_ = nullptr;
 };
 
+namespace detail {
+// What the depth-in / depth-out stage classes below share (csrc/kde_depth_stage.h is the same core in the library): the handle
+// and its stream, the results of the last batch call on the device and in pinned memory, and the format of a depth pointer.
+// A stage derives from it with its handle, its parameter struct and its six C functions, and adds its constructors, its
+// calibration, its batch call and whatever only it has.
+template <class Handle, class Params, auto DefaultParams, auto Destroy, auto DepthDevice, auto DepthHost, auto FilledDevice, auto FilledHost>
+class DepthStage {
+public:
+    static Params defaultParams()
+    {
+        Params p{};
+        check(DefaultParams(&p));
+        return p;
+    }
+    DepthStage(const DepthStage&) = delete;
+    DepthStage& operator=(const DepthStage&) = delete;
+
+    // the frames of the last batch call: out_device of that call or the object-owned buffer, float or uint16 as that call asked
+    void* depth_Device() const
+    {
+        void* p = nullptr;
+        check(DepthDevice(h_, &p));
+        return p;
+    }
+    const void* depth_Host() const
+    {
+        const void* p = nullptr;
+        check(DepthHost(h_, stream_, &p));
+        return p;
+    }
+    // the pixels that got a depth, per frame of the last batch call
+    uint32_t* filled_Device() const
+    {
+        uint32_t* p = nullptr;
+        check(FilledDevice(h_, &p));
+        return p;
+    }
+    const uint32_t* filled_Host() const
+    {
+        const uint32_t* p = nullptr;
+        check(FilledHost(h_, stream_, &p));
+        return p;
+    }
+    void setStream(void* hip_stream) { stream_ = hip_stream; }
+    Handle* handle() const { return h_; }
+
+protected:
+    DepthStage() = default;
+    ~DepthStage() { Destroy(h_); }
+    static int format(const float*) { return KDE_DEPTH_F32; }
+    static int format(const uint16_t*) { return KDE_DEPTH_U16; }
+    Handle* h_ = nullptr;       // the stage's constructor creates it
+    void* stream_ = nullptr;
+};
+}  // namespace detail
+
 // extension (no reference counterpart as a class): the registration Kinect::InitAllData asks OpenNI for (Kinect.cpp:71-75),
 // on the device (kde_reg_*): n depth frames (float* or uint16_t*) warped into the colour camera's view through a z-buffer, so
 // that depth pixel (x, y) and colour pixel (x, y) look along the same ray, as every class above assumes.  The rule is stated
 // in kde_hip.h: the nearest source pixel wins, the result is deterministic to the bit; cx and cy are kept as floats; no lens
 // distortion.  registerDepth() is asynchronous on the object's stream and capturable; the *_Host members synchronise.
-class DepthRegistration {
+class DepthRegistration
+    : public detail::DepthStage<kde_reg, kde_reg_params, kde_reg_default_params, kde_reg_destroy, kde_reg_depth_device,
+                                kde_reg_depth_host, kde_reg_filled_device, kde_reg_filled_host> {
 public:
-    static kde_reg_params defaultParams()
-    {
-        kde_reg_params p{};
-        check(kde_reg_default_params(&p));
-        return p;
-    }
     DepthRegistration(int depth_width, int depth_height, int color_width, int color_height, int max_batch = 1)
     {
         check(kde_reg_create(&h_, depth_width, depth_height, color_width, color_height, max_batch, nullptr));
@@ -1226,9 +1278,6 @@ public:
     {
         check(kde_reg_create(&h_, depth_width, depth_height, color_width, color_height, max_batch, &params));
     }
-    ~DepthRegistration() { kde_reg_destroy(h_); }
-    DepthRegistration(const DepthRegistration&) = delete;
-    DepthRegistration& operator=(const DepthRegistration&) = delete;
 
     // the two intrinsic matrices, R (row-major 3 x 3) and t (millimetres): P_colour = R * P_depth + t
     template <class MatLike>
@@ -1251,38 +1300,6 @@ public:
     {
         check(kde_reg_color_to_depth_batch(h_, n, depth_device, format(depth_device), bgr_device, bgr_frames, out_bgr_device, stream_));
     }
-    void* depth_Device() const
-    {
-        void* p = nullptr;
-        check(kde_reg_depth_device(h_, &p));
-        return p;
-    }
-    const void* depth_Host() const
-    {
-        const void* p = nullptr;
-        check(kde_reg_depth_host(h_, stream_, &p));
-        return p;
-    }
-    uint32_t* filled_Device() const
-    {
-        uint32_t* p = nullptr;
-        check(kde_reg_filled_device(h_, &p));
-        return p;
-    }
-    const uint32_t* filled_Host() const
-    {
-        const uint32_t* p = nullptr;
-        check(kde_reg_filled_host(h_, stream_, &p));
-        return p;
-    }
-    void setStream(void* hip_stream) { stream_ = hip_stream; }
-    kde_reg* handle() const { return h_; }
-
-private:
-    static int format(const float*) { return KDE_DEPTH_F32; }
-    static int format(const uint16_t*) { return KDE_DEPTH_U16; }
-    kde_reg* h_ = nullptr;
-    void* stream_ = nullptr;
 };
 
 // extension (no reference counterpart): frames of a camera with lens distortion -- OpenCV's rational model k1, k2, p1, p2, k3,
@@ -1291,14 +1308,10 @@ private:
 // is bilinear with (0, 0, 0) outside the source; depth takes the nearest valid sample or, with depth_interp 1, the bilinear
 // value where the four taps are valid and within max_gap of each other; deterministic to the bit; no rectifying rotation.
 // undistortColor() and undistortDepth() are asynchronous on the object's stream and capturable; the *_Host members synchronise.
-class LensUndistortion {
+class LensUndistortion
+    : public detail::DepthStage<kde_undist, kde_undist_params, kde_undist_default_params, kde_undist_destroy, kde_undist_depth_device,
+                                kde_undist_depth_host, kde_undist_filled_device, kde_undist_filled_host> {
 public:
-    static kde_undist_params defaultParams()
-    {
-        kde_undist_params p{};
-        check(kde_undist_default_params(&p));
-        return p;
-    }
     LensUndistortion(int src_width, int src_height, int out_width, int out_height, int max_batch = 1)
     {
         check(kde_undist_create(&h_, src_width, src_height, out_width, out_height, max_batch, nullptr));
@@ -1307,9 +1320,6 @@ public:
     {
         check(kde_undist_create(&h_, src_width, src_height, out_width, out_height, max_batch, &params));
     }
-    ~LensUndistortion() { kde_undist_destroy(h_); }
-    LensUndistortion(const LensUndistortion&) = delete;
-    LensUndistortion& operator=(const LensUndistortion&) = delete;
 
     // the distorted camera's intrinsic matrix and dist8 = k1, k2, p1, p2, k3, k4, k5, k6; the pinhole view keeps the matrix
     template <class MatLike>
@@ -1339,30 +1349,6 @@ public:
     {
         check(kde_undist_depth_batch(h_, n, depth_device, format(depth_device), format(out_device), out_device, stream_));
     }
-    void* depth_Device() const
-    {
-        void* p = nullptr;
-        check(kde_undist_depth_device(h_, &p));
-        return p;
-    }
-    const void* depth_Host() const
-    {
-        const void* p = nullptr;
-        check(kde_undist_depth_host(h_, stream_, &p));
-        return p;
-    }
-    uint32_t* filled_Device() const
-    {
-        uint32_t* p = nullptr;
-        check(kde_undist_filled_device(h_, &p));
-        return p;
-    }
-    const uint32_t* filled_Host() const
-    {
-        const uint32_t* p = nullptr;
-        check(kde_undist_filled_host(h_, stream_, &p));
-        return p;
-    }
     // [out_height][out_width] of (us, vs): OpenCV's initUndistortRectifyMap product, computed at the first request
     const float* map_Device() const
     {
@@ -1370,14 +1356,6 @@ public:
         check(kde_undist_map_device(h_, stream_, &p));
         return p;
     }
-    void setStream(void* hip_stream) { stream_ = hip_stream; }
-    kde_undist* handle() const { return h_; }
-
-private:
-    static int format(const float*) { return KDE_DEPTH_F32; }
-    static int format(const uint16_t*) { return KDE_DEPTH_U16; }
-    kde_undist* h_ = nullptr;
-    void* stream_ = nullptr;
 };
 
 // extension (no reference counterpart): a low-resolution depth frame brought to the size of its colour image on the device
@@ -1386,14 +1364,10 @@ private:
 // sensors whose depth is smaller than their colour can feed every class above.  The rule is stated in kde_hip.h; with max_gap
 // > 0 no depth is blended across more than max_gap millimetres; deterministic to the bit.  upsample() is asynchronous on the
 // object's stream and capturable; the *_Host members synchronise.
-class GuidedDepthUpsampling {
+class GuidedDepthUpsampling
+    : public detail::DepthStage<kde_upsample, kde_upsample_params, kde_upsample_default_params, kde_upsample_destroy, kde_upsample_depth_device,
+                                kde_upsample_depth_host, kde_upsample_filled_device, kde_upsample_filled_host> {
 public:
-    static kde_upsample_params defaultParams()
-    {
-        kde_upsample_params p{};
-        check(kde_upsample_default_params(&p));
-        return p;
-    }
     GuidedDepthUpsampling(int src_width, int src_height, int out_width, int out_height, int max_batch = 1)
     {
         check(kde_upsample_create(&h_, src_width, src_height, out_width, out_height, max_batch, nullptr));
@@ -1402,9 +1376,6 @@ public:
     {
         check(kde_upsample_create(&h_, src_width, src_height, out_width, out_height, max_batch, &params));
     }
-    ~GuidedDepthUpsampling() { kde_upsample_destroy(h_); }
-    GuidedDepthUpsampling(const GuidedDepthUpsampling&) = delete;
-    GuidedDepthUpsampling& operator=(const GuidedDepthUpsampling&) = delete;
 
     // n depth frames back to back, the guide bgr_frames = 1 (one image for every frame) or n images of the output size; the
     // output format is the type of out_device (nullptr of that type: the object-owned buffer)
@@ -1414,40 +1385,8 @@ public:
         check(kde_upsample_depth_batch(h_, n, depth_device, format(depth_device), bgr_device, bgr_frames, format(out_device), out_device,
                                        stream_));
     }
-    void* depth_Device() const
-    {
-        void* p = nullptr;
-        check(kde_upsample_depth_device(h_, &p));
-        return p;
-    }
-    const void* depth_Host() const
-    {
-        const void* p = nullptr;
-        check(kde_upsample_depth_host(h_, stream_, &p));
-        return p;
-    }
-    uint32_t* filled_Device() const
-    {
-        uint32_t* p = nullptr;
-        check(kde_upsample_filled_device(h_, &p));
-        return p;
-    }
-    const uint32_t* filled_Host() const
-    {
-        const uint32_t* p = nullptr;
-        check(kde_upsample_filled_host(h_, stream_, &p));
-        return p;
-    }
     // range[k] for k = |db| + |dg| + |dr| = 0 .. 765, as the kernel reads it
     void rangeTable(float (&table_host)[766]) const { check(kde_upsample_range_table(h_, table_host, 766)); }
-    void setStream(void* hip_stream) { stream_ = hip_stream; }
-    kde_upsample* handle() const { return h_; }
-
-private:
-    static int format(const float*) { return KDE_DEPTH_F32; }
-    static int format(const uint16_t*) { return KDE_DEPTH_U16; }
-    kde_upsample* h_ = nullptr;
-    void* stream_ = nullptr;
 };
 
 // extension (no reference counterpart): the holes of a depth frame filled on the device under the guide of its colour image
@@ -1457,22 +1396,15 @@ private:
 // pixels into one.  iterations * radius bounds how far a fill reaches.  The rule is stated in kde_hip.h; with max_gap > 0 no
 // depth is blended across more than max_gap millimetres; deterministic to the bit.  fill() is asynchronous on the object's
 // stream and capturable; the *_Host members synchronise.
-class DepthHoleFilling {
+class DepthHoleFilling
+    : public detail::DepthStage<kde_holefill, kde_holefill_params, kde_holefill_default_params, kde_holefill_destroy, kde_holefill_depth_device,
+                                kde_holefill_depth_host, kde_holefill_filled_device, kde_holefill_filled_host> {
 public:
-    static kde_holefill_params defaultParams()
-    {
-        kde_holefill_params p{};
-        check(kde_holefill_default_params(&p));
-        return p;
-    }
     DepthHoleFilling(int width, int height, int max_batch = 1) { check(kde_holefill_create(&h_, width, height, max_batch, nullptr)); }
     DepthHoleFilling(int width, int height, int max_batch, const kde_holefill_params& params)
     {
         check(kde_holefill_create(&h_, width, height, max_batch, &params));
     }
-    ~DepthHoleFilling() { kde_holefill_destroy(h_); }
-    DepthHoleFilling(const DepthHoleFilling&) = delete;
-    DepthHoleFilling& operator=(const DepthHoleFilling&) = delete;
 
     // n depth frames back to back, the guide bgr_frames = 1 (one image for every frame) or n images; the output format is the
     // type of out_device (nullptr of that type: the object-owned buffer), which must not overlap depth_device; pass_of_device:
@@ -1482,30 +1414,6 @@ public:
     {
         check(kde_holefill_fill_batch(h_, n, depth_device, format(depth_device), bgr_device, bgr_frames, format(out_device), out_device,
                                       pass_of_device, stream_));
-    }
-    void* depth_Device() const
-    {
-        void* p = nullptr;
-        check(kde_holefill_depth_device(h_, &p));
-        return p;
-    }
-    const void* depth_Host() const
-    {
-        const void* p = nullptr;
-        check(kde_holefill_depth_host(h_, stream_, &p));
-        return p;
-    }
-    uint32_t* filled_Device() const
-    {
-        uint32_t* p = nullptr;
-        check(kde_holefill_filled_device(h_, &p));
-        return p;
-    }
-    const uint32_t* filled_Host() const
-    {
-        const uint32_t* p = nullptr;
-        check(kde_holefill_filled_host(h_, stream_, &p));
-        return p;
     }
     uint32_t* remaining_Device() const
     {
@@ -1529,14 +1437,6 @@ public:
     // space[(2 radius + 1)^2] (capacity: the entries table_host holds) and range[k] for k = |db| + |dg| + |dr| = 0 .. 765
     void spaceTable(float* table_host, int capacity) const { check(kde_holefill_space_table(h_, table_host, capacity)); }
     void rangeTable(float (&table_host)[766]) const { check(kde_holefill_range_table(h_, table_host, 766)); }
-    void setStream(void* hip_stream) { stream_ = hip_stream; }
-    kde_holefill* handle() const { return h_; }
-
-private:
-    static int format(const float*) { return KDE_DEPTH_F32; }
-    static int format(const uint16_t*) { return KDE_DEPTH_U16; }
-    kde_holefill* h_ = nullptr;
-    void* stream_ = nullptr;
 };
 
 }  // namespace kde

@@ -133,14 +133,11 @@ __global__ __launch_bounds__(kThreads) void holefill_kernel(HolefillLaunch L)
     uint8_t* pframe = L.pass + (size_t)frame * px;
     // the state of pass p0 at a pixel of the frame: pass 0 of the rule in the first launch, the stored state later
     auto state_at = [&](size_t at) {
-        const float d = in_f32 ? reinterpret_cast<const float*>(sframe)[at] : (float)reinterpret_cast<const uint16_t*>(sframe)[at];
+        const float d = load_depth(sframe, in_f32, at);
         if (!L.first) return d;
         return (d > L.z_min && d < L.z_max) ? d : 0.0f;     // a NaN fails
     };
-    auto store = [&](size_t at, float z) {
-        if (out_f32) reinterpret_cast<float*>(dframe)[at] = z;
-        else reinterpret_cast<uint16_t*>(dframe)[at] = depth_to_u16(z);
-    };
+    auto store = [&](size_t at, float z) { store_depth(dframe, out_f32, at, z); };
 
     float mine[kPerThread];
     bool inside[kPerThread];
@@ -173,7 +170,7 @@ __global__ __launch_bounds__(kThreads) void holefill_kernel(HolefillLaunch L)
         const uint8_t* gframe = L.bgr + (L.bgr_frames == 1 ? (size_t)0 : (size_t)frame) * px * 3;
         // k of two cells of the frame is at most 765; against a cell outside the frame (word 0, bit 24 clear) the SAD reaches 766:
         // that tap is absent by its depth of 0, and the entries behind the table are 0 so that its weight is one too
-        for (int k = tid; k < 768; k += kThreads) s_range[k] = k < kHolefillRange ? L.range[k] : 0.0f;
+        for (int k = tid; k < 768; k += kThreads) s_range[k] = k < kColourRange ? L.range[k] : 0.0f;
         if (tid < D * D) s_space[tid] = L.space[tid];
         for (int idx = tid; idx < sw * sh; idx += kThreads) {
             const int cy = idx / sw, cx = idx - cy * sw;
@@ -183,8 +180,7 @@ __global__ __launch_bounds__(kThreads) void holefill_kernel(HolefillLaunch L)
             if ((unsigned)x < (unsigned)L.w && (unsigned)y < (unsigned)L.h) {
                 const size_t at = (size_t)y * (unsigned)L.w + (unsigned)x;
                 z = state_at(at);
-                const uint8_t* p = gframe + at * 3;
-                c = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | (1u << 24);
+                c = pack_bgr(gframe + at * 3) | (1u << 24);
             }
             s_z[0][cy * PW + cx] = z;
             s_c[cy * PW + cx] = c;
@@ -250,7 +246,7 @@ __global__ __launch_bounds__(kThreads) void holefill_kernel(HolefillLaunch L)
         s_count[1][tid >> 6] = remaining;
     }
     __syncthreads();
-    if (tid < 2) L.partial[((size_t)frame * gridDim.x + blockIdx.x) * 2 + tid] = (s_count[tid][0] + s_count[tid][1]) + (s_count[tid][2] + s_count[tid][3]);
+    if (tid < 2) L.partial[((size_t)frame * gridDim.x + blockIdx.x) * 2 + tid] = block_sum_u32(s_count[tid]);
 }
 
 // H2: grid n, block 256

@@ -9,9 +9,7 @@ struct kde_holefill {
     kde_holefill_params p{};
     int fuse = 1;                           // passes per launch: p.passes_per_launch, or the library's choice for the radius
     unsigned groups = 0;                    // workgroups per frame
-    int n_last = 0;                         // frames of the last fill_batch (0: none yet)
-    int format_last = KDE_DEPTH_F32;        // its out_format
-    void* out_last = nullptr;               // where it wrote: depth or the caller's buffer
+    DepthStage stage;                       // the last fill_batch; depth [max_batch][H][W]
     std::vector<float> space_host;          // space[(2r + 1)^2]
     std::vector<float> range_host;          // range[766]
     DevBuf<float> space, range;
@@ -19,18 +17,13 @@ struct kde_holefill {
     DevBuf<uint8_t> pass;                   // [max_batch][H][W]: pass_of of a call without pass_of_dev
     DevBuf<uint32_t> partial;               // [max_batch][groups][2]
     DevBuf<uint32_t> counts;                // filled[max_batch], then remaining[max_batch]
-    DevBuf<float> depth;                    // [max_batch][H][W]: floats, or uint16 in the same bytes
     PinnedBuf<uint32_t> filled_host, remaining_host;
-    PinnedBuf<float> depth_host;
 };
 
 static const kde_holefill_params kHolefillDefaults = {2, 8, 3, 2.0f, 30.0f, 0.0f, 0, 0.0f, FLT_MAX, 0};
 // the library's passes per launch for radius 1, 2, 3: measured on the MI355X ("Depth hole filling").  At radius 3
 // with the guard fusing did not beat one pass per launch on any frame set: the choice there is 1.
 static const int kHolefillFuse[kHolefillMaxRadius + 1] = {0, 4, 2, 2};
-
-static bool depth_format_ok(int f) { return f == KDE_DEPTH_F32 || f == KDE_DEPTH_U16; }
-static size_t depth_element(int f) { return f == KDE_DEPTH_U16 ? sizeof(uint16_t) : sizeof(float); }
 
 // radius 2, 8 passes, 3 taps, sigma_space 2, sigma_color 30 (K0's constant, the same squared-L1 form), no guard, every finite
 // positive depth, the library's passes per launch
@@ -54,12 +47,11 @@ extern "C" int kde_holefill_create(kde_holefill** out, int width, int height, in
                 kHolefillMaxIterations);
     const int side = 2 * q.radius + 1, taps = side * side - 1;
     KDE_REQUIRE(q.min_taps >= 1 && q.min_taps <= taps, "%s: min_taps=%d outside 1..%d (radius %d)", who, q.min_taps, taps, q.radius);
-    KDE_REQUIRE(std::isfinite(q.sigma_space) && q.sigma_space > 0.0f, "%s: sigma_space=%g must be finite and > 0", who, (double)q.sigma_space);
-    KDE_REQUIRE(std::isfinite(q.sigma_color) && q.sigma_color > 0.0f, "%s: sigma_color=%g must be finite and > 0", who, (double)q.sigma_color);
-    KDE_REQUIRE(std::isfinite(q.max_gap) && q.max_gap >= 0.0f, "%s: max_gap=%g must be finite and >= 0 (0: no guard)", who, (double)q.max_gap);
+    KDE_TRY(check_sigma(who, "sigma_space", q.sigma_space));
+    KDE_TRY(check_sigma(who, "sigma_color", q.sigma_color));
+    KDE_TRY(check_max_gap(who, q.max_gap));
     KDE_REQUIRE(q.gap_rule == 0 || q.gap_rule == 1, "%s: gap_rule=%d is neither 0 (heaviest) nor 1 (farthest)", who, q.gap_rule);
-    KDE_REQUIRE(std::isfinite(q.z_min) && q.z_min >= 0.0f, "%s: z_min=%g must be finite and >= 0", who, (double)q.z_min);
-    KDE_REQUIRE(q.z_min < q.z_max, "%s: z_min=%g must be below z_max=%g", who, (double)q.z_min, (double)q.z_max);
+    KDE_TRY(check_z_range(who, q.z_min, q.z_max));
     KDE_REQUIRE(q.passes_per_launch >= 0 && q.passes_per_launch <= kHolefillMaxFuse, "%s: passes_per_launch=%d outside 0..%d", who,
                 q.passes_per_launch, kHolefillMaxFuse);
     kde_holefill* h = new_handle<kde_holefill>(width, height, max_batch);
@@ -69,7 +61,7 @@ extern "C" int kde_holefill_create(kde_holefill** out, int width, int height, in
     h->groups = holefill_groups(width, height);
     try {
         h->space_host.resize((size_t)side * side);
-        h->range_host.resize(kHolefillRange);
+        h->range_host.resize(kColourRange);
     } catch (const std::bad_alloc&) {
         delete h;
         return fail(KDE_ERR_NOMEM, "%s: out of host memory", who);
@@ -78,22 +70,21 @@ extern "C" int kde_holefill_create(kde_holefill** out, int width, int height, in
         for (int dx = -q.radius; dx <= q.radius; dx++)
             h->space_host[(size_t)(dy + q.radius) * side + dx + q.radius] =
                 (float)std::exp(-(double)(dx * dx + dy * dy) / (2.0 * (double)q.sigma_space * (double)q.sigma_space));
-    for (int k = 0; k < kHolefillRange; k++)
-        h->range_host[k] = (float)std::exp(-(double)(k * k) / (2.0 * (double)q.sigma_color * (double)q.sigma_color));
+    colour_range_table(q.sigma_color, h->range_host.data());
     if (h->device >= 0) {
         const size_t px = (size_t)max_batch * width * height;
         const bool states = q.iterations > h->fuse;         // more than one launch
         int rc = h->counts.alloc((size_t)max_batch * 2);
         if (rc == KDE_OK) rc = h->partial.alloc((size_t)max_batch * h->groups * 2);
-        if (rc == KDE_OK) rc = h->depth.alloc(px);
+        if (rc == KDE_OK) rc = h->stage.depth.alloc(px);
         if (rc == KDE_OK) rc = h->pass.alloc(px);
         if (rc == KDE_OK && states) rc = h->state[0].alloc(px);
         if (rc == KDE_OK && q.iterations > 2 * h->fuse) rc = h->state[1].alloc(px);
         if (rc == KDE_OK) rc = h->space.alloc(h->space_host.size());
-        if (rc == KDE_OK) rc = h->range.alloc((size_t)kHolefillRange);
+        if (rc == KDE_OK) rc = h->range.alloc((size_t)kColourRange);
         if (rc == KDE_OK && hipMemcpy(h->space.p, h->space_host.data(), h->space_host.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
             rc = fail(KDE_ERR_HIP, "%s: the space table could not be copied to the device", who);
-        if (rc == KDE_OK && hipMemcpy(h->range.p, h->range_host.data(), kHolefillRange * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+        if (rc == KDE_OK && hipMemcpy(h->range.p, h->range_host.data(), kColourRange * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
             rc = fail(KDE_ERR_HIP, "%s: the range table could not be copied to the device", who);
         if (rc != KDE_OK) {
             delete h;
@@ -122,11 +113,7 @@ extern "C" int kde_holefill_space_table(kde_holefill* h, float* table_host, int 
 
 extern "C" int kde_holefill_range_table(kde_holefill* h, float* table_host, int capacity)
 {
-    const char* who = "kde_holefill_range_table";
-    KDE_REQUIRE(h && table_host, "%s: null argument", who);
-    KDE_REQUIRE(capacity >= kHolefillRange, "%s: capacity=%d is below the %d entries of the table", who, capacity, kHolefillRange);
-    std::memcpy(table_host, h->range_host.data(), kHolefillRange * sizeof(float));
-    return KDE_OK;
+    return copy_range_table("kde_holefill_range_table", h ? &h->range_host : nullptr, table_host, capacity);
 }
 
 extern "C" int kde_holefill_passes_per_launch(kde_holefill* h, int* out)
@@ -141,25 +128,13 @@ extern "C" int kde_holefill_fill_batch(kde_holefill* h, int n, const void* depth
 {
     const char* who = "kde_holefill_fill_batch";
     KDE_REQUIRE(h && depth_dev && bgr_dev, "%s: null argument", who);
-    KDE_REQUIRE(n >= 1 && n <= h->max_batch, "%s: n=%d outside 1..max_batch=%d", who, n, h->max_batch);
-    KDE_REQUIRE(bgr_frames == 1 || bgr_frames == n, "%s: bgr_frames=%d is neither 1 nor n=%d", who, bgr_frames, n);
-    KDE_REQUIRE(depth_format_ok(depth_format), "%s: the unknown depth format %d", who, depth_format);
-    KDE_REQUIRE(reinterpret_cast<uintptr_t>(depth_dev) % depth_element(depth_format) == 0, "%s: depth_dev is not %d-byte aligned", who,
-                (int)depth_element(depth_format));
-    KDE_REQUIRE(depth_format_ok(out_format), "%s: the unknown output format %d", who, out_format);
-    KDE_REQUIRE(reinterpret_cast<uintptr_t>(out_dev) % depth_element(out_format) == 0, "%s: out_dev is not %d-byte aligned", who,
-                (int)depth_element(out_format));
-    const size_t px = (size_t)n * h->width * h->height;
-    // A workgroup reads the halo of its tile while its neighbours write theirs.  The buffer that is written is the caller's or
-    // the object's own, which a caller holds after kde_holefill_depth_device (a device-less object has none).
-    if (const void* written = out_dev ? out_dev : static_cast<void*>(h->depth.p)) {
-        const uintptr_t d0 = reinterpret_cast<uintptr_t>(depth_dev), d1 = d0 + px * depth_element(depth_format);
-        const uintptr_t o0 = reinterpret_cast<uintptr_t>(written), o1 = o0 + px * depth_element(out_format);
-        KDE_REQUIRE(o1 <= d0 || d1 <= o0, "%s: %s overlaps depth_dev (in place is not supported)", who,
-                    out_dev ? "out_dev" : "the object-owned output buffer, which out_dev == NULL selects,");
-    }
-    KDE_ON_DEVICE(h, who);
-    if (h->device < 0) return fail(KDE_ERR_HIP, "%s: the handle was created on a host without a device", who);
+    KDE_TRY(check_batch_n(who, n, h->max_batch));
+    KDE_TRY(check_bgr_frames(who, bgr_frames, n));
+    KDE_TRY(check_depth_in(who, depth_dev, depth_format));
+    KDE_TRY(check_depth_out(who, out_dev, out_format));
+    // a workgroup reads the halo of its tile while its neighbours write theirs
+    KDE_TRY(h->stage.check_not_in_place(who, depth_dev, depth_format, out_dev, out_format, (size_t)n * h->width * h->height));
+    KDE_TRY(check_has_device(who, h->device));
     HolefillLaunch a{};
     a.n = n;
     a.w = h->width;
@@ -176,7 +151,7 @@ extern "C" int kde_holefill_fill_batch(kde_holefill* h, int n, const void* depth
     a.depth_format = depth_format;
     a.bgr = bgr_dev;
     a.bgr_frames = bgr_frames;
-    a.out = out_dev ? out_dev : h->depth.p;
+    a.out = h->stage.written(out_dev);
     a.out_format = out_format;
     a.state[0] = h->state[0].p;
     a.state[1] = h->state[1].p;
@@ -187,63 +162,11 @@ extern "C" int kde_holefill_fill_batch(kde_holefill* h, int n, const void* depth
     a.filled = h->counts.p;
     a.remaining = h->counts.p + h->max_batch;
     KDE_TRY(launch_holefill(a, as_stream(stream)));
-    h->n_last = n;
-    h->format_last = out_format;
-    h->out_last = a.out;
+    h->stage.finished(n, out_format, a.out);
     return KDE_OK;
 }
 
-extern "C" int kde_holefill_depth_device(kde_holefill* h, void** out)
-{
-    KDE_REQUIRE(h && out, "kde_holefill_depth_device: null argument");
-    KDE_REQUIRE(h->n_last > 0, "kde_holefill_depth_device: kde_holefill_fill_batch was not called");
-    *out = h->out_last;
-    return KDE_OK;
-}
-
-extern "C" int kde_holefill_depth_host(kde_holefill* h, void* stream, const void** out)
-{
-    const char* who = "kde_holefill_depth_host";
-    KDE_REQUIRE(h && out, "%s: null argument", who);
-    KDE_REQUIRE(h->n_last > 0, "%s: kde_holefill_fill_batch was not called", who);
-    KDE_ON_DEVICE(h, who);
-    const size_t px = (size_t)h->width * h->height;
-    KDE_TRY(h->depth_host.ensure((size_t)h->max_batch * px));
-    hipStream_t s = as_stream(stream);
-    KDE_HIP_TRY(hipMemcpyAsync(h->depth_host.p, h->out_last, (size_t)h->n_last * px * depth_element(h->format_last), hipMemcpyDeviceToHost, s));
-    KDE_HIP_TRY(hipStreamSynchronize(s));
-    *out = h->depth_host.p;
-    return KDE_OK;
-}
-
-extern "C" int kde_holefill_filled_device(kde_holefill* h, uint32_t** out)
-{
-    KDE_REQUIRE(h && out, "kde_holefill_filled_device: null argument");
-    KDE_REQUIRE(h->n_last > 0, "kde_holefill_filled_device: kde_holefill_fill_batch was not called");
-    *out = h->counts.p;
-    return KDE_OK;
-}
-
-extern "C" int kde_holefill_filled_host(kde_holefill* h, void* stream, const uint32_t** out)
-{
-    KDE_REQUIRE(h && out, "kde_holefill_filled_host: null argument");
-    KDE_REQUIRE(h->n_last > 0, "kde_holefill_filled_host: kde_holefill_fill_batch was not called");
-    return host_mirror("kde_holefill_filled_host", h->device, h->counts.p, (size_t)h->n_last, (size_t)h->max_batch, h->filled_host,
-                       as_stream(stream), out);
-}
-
-extern "C" int kde_holefill_remaining_device(kde_holefill* h, uint32_t** out)
-{
-    KDE_REQUIRE(h && out, "kde_holefill_remaining_device: null argument");
-    KDE_REQUIRE(h->n_last > 0, "kde_holefill_remaining_device: kde_holefill_fill_batch was not called");
-    *out = h->counts.p + h->max_batch;
-    return KDE_OK;
-}
-
-extern "C" int kde_holefill_remaining_host(kde_holefill* h, void* stream, const uint32_t** out)
-{
-    KDE_REQUIRE(h && out, "kde_holefill_remaining_host: null argument");
-    KDE_REQUIRE(h->n_last > 0, "kde_holefill_remaining_host: kde_holefill_fill_batch was not called");
-    return host_mirror("kde_holefill_remaining_host", h->device, h->counts.p + h->max_batch, (size_t)h->n_last, (size_t)h->max_batch,
-                       h->remaining_host, as_stream(stream), out);
-}
+KDE_STAGE_DEPTH_GETTERS(kde_holefill_depth_device, kde_holefill_depth_host, kde_holefill, "kde_holefill_fill_batch", (size_t)h->width * h->height)
+KDE_STAGE_COUNT_GETTERS(kde_holefill_filled_device, kde_holefill_filled_host, kde_holefill, "kde_holefill_fill_batch", h->counts.p, h->filled_host)
+KDE_STAGE_COUNT_GETTERS(kde_holefill_remaining_device, kde_holefill_remaining_host, kde_holefill, "kde_holefill_fill_batch",
+                        h->counts.p + h->max_batch, h->remaining_host)

@@ -9,20 +9,13 @@ struct kde_reg {
     kde_reg_params p{};
     RegCalib c{};
     bool calibrated = false;
-    int n_last = 0;                         // frames of the last register_batch (0: none yet)
-    int format_last = KDE_DEPTH_F32;        // its out_format
-    void* out_last = nullptr;               // where it wrote: depth or the caller's buffer
+    DepthStage stage;                       // the last register_batch; depth [max_batch][color_h][color_w]
     DevBuf<uint32_t> zbuf;                  // [max_batch][reg_zstride(color_w * color_h)]
     DevBuf<uint32_t> filled;                // [max_batch]
-    DevBuf<float> depth;                    // [max_batch][color_h][color_w]: floats, or uint16 in the same bytes
     PinnedBuf<uint32_t> filled_host;
-    PinnedBuf<float> depth_host;
 };
 
 static const kde_reg_params kRegDefaults = {0.0f, FLT_MAX, 0};
-
-static bool depth_format_ok(int f) { return f == KDE_DEPTH_F32 || f == KDE_DEPTH_U16; }
-static size_t depth_element(int f) { return f == KDE_DEPTH_U16 ? sizeof(uint16_t) : sizeof(float); }
 
 // Kinect.cpp:71-75 takes no parameter: every finite positive depth is registered, one target pixel per source pixel
 extern "C" int kde_reg_default_params(kde_reg_params* p)
@@ -43,9 +36,7 @@ extern "C" int kde_reg_create(kde_reg** out, int depth_w, int depth_h, int color
     KDE_REQUIRE(depth_w <= kRegMaxSide && depth_h <= kRegMaxSide && color_w <= kRegMaxSide && color_h <= kRegMaxSide,
                 "%s: a side above %d is not an exact float", who, kRegMaxSide);
     const kde_reg_params q = p ? *p : kRegDefaults;
-    KDE_REQUIRE(std::isfinite(q.z_min) && q.z_min >= 0.0f, "%s: z_min=%g must be finite and >= 0 (the key order needs positive z)", who,
-                (double)q.z_min);
-    KDE_REQUIRE(q.z_min < q.z_max, "%s: z_min=%g must be below z_max=%g", who, (double)q.z_min, (double)q.z_max);
+    KDE_TRY(check_z_range(who, q.z_min, q.z_max, " (the key order needs positive z)"));
     KDE_REQUIRE(q.max_splat >= 0 && q.max_splat <= kRegMaxSplat, "%s: max_splat=%d outside 0..%d", who, q.max_splat, kRegMaxSplat);
     kde_reg* h = new_handle<kde_reg>(depth_w, depth_h, max_batch);
     if (!h) return fail(KDE_ERR_NOMEM, "%s: out of host memory", who);
@@ -56,7 +47,7 @@ extern "C" int kde_reg_create(kde_reg** out, int depth_w, int depth_h, int color
         const size_t px = (size_t)color_w * color_h;
         int rc = h->zbuf.alloc((size_t)max_batch * reg_zstride(px));
         if (rc == KDE_OK) rc = h->filled.alloc((size_t)max_batch);
-        if (rc == KDE_OK) rc = h->depth.alloc((size_t)max_batch * px);
+        if (rc == KDE_OK) rc = h->stage.depth.alloc((size_t)max_batch * px);
         if (rc != KDE_OK) {
             delete h;
             return rc;
@@ -102,10 +93,8 @@ extern "C" int kde_reg_set_calibration(kde_reg* h, const double* Kd9, const doub
 // what register_batch and color_to_depth_batch ask of the object, n and the depth map alike
 static int check_depth(const kde_reg* h, const char* who, int n, const void* depth_dev, int depth_format)
 {
-    KDE_REQUIRE(n >= 1 && n <= h->max_batch, "%s: n=%d outside 1..max_batch=%d", who, n, h->max_batch);
-    KDE_REQUIRE(depth_format_ok(depth_format), "%s: the unknown depth format %d", who, depth_format);
-    KDE_REQUIRE(reinterpret_cast<uintptr_t>(depth_dev) % depth_element(depth_format) == 0, "%s: depth_dev is not %d-byte aligned", who,
-                (int)depth_element(depth_format));
+    KDE_TRY(check_batch_n(who, n, h->max_batch));
+    KDE_TRY(check_depth_in(who, depth_dev, depth_format));
     KDE_REQUIRE(h->calibrated, "%s: kde_reg_set_calibration was not called", who);
     return KDE_OK;
 }
@@ -134,20 +123,15 @@ extern "C" int kde_reg_register_batch(kde_reg* h, int n, const void* depth_dev, 
     const char* who = "kde_reg_register_batch";
     KDE_REQUIRE(h && depth_dev, "%s: null argument", who);
     KDE_TRY(check_depth(h, who, n, depth_dev, depth_format));
-    KDE_REQUIRE(depth_format_ok(out_format), "%s: the unknown output format %d", who, out_format);
-    KDE_REQUIRE(reinterpret_cast<uintptr_t>(out_dev) % depth_element(out_format) == 0, "%s: out_dev is not %d-byte aligned", who,
-                (int)depth_element(out_format));
-    KDE_ON_DEVICE(h, who);
-    if (h->device < 0) return fail(KDE_ERR_HIP, "%s: the handle was created on a host without a device", who);
+    KDE_TRY(check_depth_out(who, out_dev, out_format));
+    KDE_TRY(check_has_device(who, h->device));
     RegLaunch a = launch_of(h, n, depth_dev, depth_format);
     a.zbuf = h->zbuf.p;
     a.filled = h->filled.p;
-    a.out = out_dev ? out_dev : h->depth.p;
+    a.out = h->stage.written(out_dev);
     a.out_format = out_format;
     KDE_TRY(launch_reg(a, as_stream(stream)));
-    h->n_last = n;
-    h->format_last = out_format;
-    h->out_last = a.out;
+    h->stage.finished(n, out_format, a.out);
     return KDE_OK;
 }
 
@@ -158,51 +142,14 @@ extern "C" int kde_reg_color_to_depth_batch(kde_reg* h, int n, const void* depth
     const char* who = "kde_reg_color_to_depth_batch";
     KDE_REQUIRE(h && depth_dev && bgr_dev && out_bgr_dev, "%s: null argument", who);
     KDE_TRY(check_depth(h, who, n, depth_dev, depth_format));
-    KDE_REQUIRE(bgr_frames == 1 || bgr_frames == n, "%s: bgr_frames=%d is neither 1 nor n=%d", who, bgr_frames, n);
-    KDE_ON_DEVICE(h, who);
-    if (h->device < 0) return fail(KDE_ERR_HIP, "%s: the handle was created on a host without a device", who);
+    KDE_TRY(check_bgr_frames(who, bgr_frames, n));
+    KDE_TRY(check_has_device(who, h->device));
     return launch_reg_gather(launch_of(h, n, depth_dev, depth_format), bgr_dev, bgr_frames, out_bgr_dev, as_stream(stream));
 }
 
-// Kinect.cpp:71-75: the registered frames of the last call (out_dev of that call, or the object-owned buffer)
-extern "C" int kde_reg_depth_device(kde_reg* h, void** out)
-{
-    KDE_REQUIRE(h && out, "kde_reg_depth_device: null argument");
-    KDE_REQUIRE(h->n_last > 0, "kde_reg_depth_device: kde_reg_register_batch was not called");
-    *out = h->out_last;
-    return KDE_OK;
-}
+// Kinect.cpp:71-75: the registered frames of the last call (out_dev of that call, or the object-owned buffer) on the device,
+// and, as Kinect.cpp hands its frames to the host, the same in pinned memory, ready when the call returns
+KDE_STAGE_DEPTH_GETTERS(kde_reg_depth_device, kde_reg_depth_host, kde_reg, "kde_reg_register_batch", (size_t)h->color_w * h->color_h)
 
-// Kinect.cpp:71-75 hands its frames to the host: the same in pinned memory, ready when the call returns
-extern "C" int kde_reg_depth_host(kde_reg* h, void* stream, const void** out)
-{
-    const char* who = "kde_reg_depth_host";
-    KDE_REQUIRE(h && out, "%s: null argument", who);
-    KDE_REQUIRE(h->n_last > 0, "%s: kde_reg_register_batch was not called", who);
-    KDE_ON_DEVICE(h, who);
-    const size_t px = (size_t)h->color_w * h->color_h;
-    KDE_TRY(h->depth_host.ensure((size_t)h->max_batch * px));
-    hipStream_t s = as_stream(stream);
-    KDE_HIP_TRY(hipMemcpyAsync(h->depth_host.p, h->out_last, (size_t)h->n_last * px * depth_element(h->format_last), hipMemcpyDeviceToHost, s));
-    KDE_HIP_TRY(hipStreamSynchronize(s));
-    *out = h->depth_host.p;
-    return KDE_OK;
-}
-
-// Kinect.cpp:71-75: how many pixels of the image viewpoint got a depth, per frame, on the device
-extern "C" int kde_reg_filled_device(kde_reg* h, uint32_t** out)
-{
-    KDE_REQUIRE(h && out, "kde_reg_filled_device: null argument");
-    KDE_REQUIRE(h->n_last > 0, "kde_reg_filled_device: kde_reg_register_batch was not called");
-    *out = h->filled.p;
-    return KDE_OK;
-}
-
-// Kinect.cpp:71-75: the same in pinned memory, ready when the call returns
-extern "C" int kde_reg_filled_host(kde_reg* h, void* stream, const uint32_t** out)
-{
-    KDE_REQUIRE(h && out, "kde_reg_filled_host: null argument");
-    KDE_REQUIRE(h->n_last > 0, "kde_reg_filled_host: kde_reg_register_batch was not called");
-    return host_mirror("kde_reg_filled_host", h->device, h->filled.p, (size_t)h->n_last, (size_t)h->max_batch, h->filled_host,
-                       as_stream(stream), out);
-}
+// Kinect.cpp:71-75: how many pixels of the image viewpoint got a depth, per frame, on the device and in pinned memory
+KDE_STAGE_COUNT_GETTERS(kde_reg_filled_device, kde_reg_filled_host, kde_reg, "kde_reg_register_batch", h->filled.p, h->filled_host)

@@ -11,20 +11,13 @@ struct kde_undist {
     UndistCalib c{};
     bool calibrated = false;
     bool map_valid = false;                 // map holds the map of c
-    int n_last = 0;                         // frames of the last depth_batch (0: none yet)
-    int format_last = KDE_DEPTH_F32;        // its out_format
-    void* out_last = nullptr;               // where it wrote: depth or the caller's buffer
+    DepthStage stage;                       // the last depth_batch; depth [max_batch][out_h][out_w]
     DevBuf<uint32_t> filled;                // [max_batch]
-    DevBuf<float> depth;                    // [max_batch][out_h][out_w]: floats, or uint16 in the same bytes
     DevBuf<float2> map;                     // [out_h][out_w] of (us, vs)
     PinnedBuf<uint32_t> filled_host;
-    PinnedBuf<float> depth_host;
 };
 
 static const kde_undist_params kUndistDefaults = {0.0f, FLT_MAX, 0, 0.0f};
-
-static bool depth_format_ok(int f) { return f == KDE_DEPTH_F32 || f == KDE_DEPTH_U16; }
-static size_t depth_element(int f) { return f == KDE_DEPTH_U16 ? sizeof(uint16_t) : sizeof(float); }
 
 // every finite positive depth, the nearest sample: nothing is blended unless the caller names a max_gap
 extern "C" int kde_undist_default_params(kde_undist_params* p)
@@ -44,8 +37,7 @@ extern "C" int kde_undist_create(kde_undist** out, int src_w, int src_h, int out
     KDE_REQUIRE(src_w <= kRegMaxSide && src_h <= kRegMaxSide && out_w <= kRegMaxSide && out_h <= kRegMaxSide,
                 "%s: a side above %d is not an exact float", who, kRegMaxSide);
     const kde_undist_params q = p ? *p : kUndistDefaults;
-    KDE_REQUIRE(std::isfinite(q.z_min) && q.z_min >= 0.0f, "%s: z_min=%g must be finite and >= 0", who, (double)q.z_min);
-    KDE_REQUIRE(q.z_min < q.z_max, "%s: z_min=%g must be below z_max=%g", who, (double)q.z_min, (double)q.z_max);
+    KDE_TRY(check_z_range(who, q.z_min, q.z_max));
     KDE_REQUIRE(q.depth_interp == 0 || q.depth_interp == 1, "%s: depth_interp=%d is neither 0 (nearest) nor 1 (guarded bilinear)", who,
                 q.depth_interp);
     KDE_REQUIRE(q.depth_interp == 0 || (std::isfinite(q.max_gap) && q.max_gap > 0.0f),
@@ -58,7 +50,7 @@ extern "C" int kde_undist_create(kde_undist** out, int src_w, int src_h, int out
     if (h->device >= 0) {
         const size_t px = (size_t)out_w * out_h;
         int rc = h->filled.alloc((size_t)max_batch);
-        if (rc == KDE_OK) rc = h->depth.alloc((size_t)max_batch * px);
+        if (rc == KDE_OK) rc = h->stage.depth.alloc((size_t)max_batch * px);
         if (rc == KDE_OK) rc = h->map.alloc(px);
         if (rc != KDE_OK) {
             delete h;
@@ -120,11 +112,10 @@ extern "C" int kde_undist_color_batch(kde_undist* h, int n, const uint8_t* bgr_d
 {
     const char* who = "kde_undist_color_batch";
     KDE_REQUIRE(h && bgr_dev && out_bgr_dev, "%s: null argument", who);
-    KDE_REQUIRE(n >= 1 && n <= h->max_batch, "%s: n=%d outside 1..max_batch=%d", who, n, h->max_batch);
-    KDE_REQUIRE(bgr_frames == 1 || bgr_frames == n, "%s: bgr_frames=%d is neither 1 nor n=%d", who, bgr_frames, n);
+    KDE_TRY(check_batch_n(who, n, h->max_batch));
+    KDE_TRY(check_bgr_frames(who, bgr_frames, n));
     KDE_REQUIRE(h->calibrated, "%s: kde_undist_set_calibration was not called", who);
-    KDE_ON_DEVICE(h, who);
-    if (h->device < 0) return fail(KDE_ERR_HIP, "%s: the handle was created on a host without a device", who);
+    KDE_TRY(check_has_device(who, h->device));
     return launch_undist_color(launch_of(h, n), bgr_dev, bgr_frames, out_bgr_dev, as_stream(stream));
 }
 
@@ -133,67 +124,24 @@ extern "C" int kde_undist_depth_batch(kde_undist* h, int n, const void* depth_de
 {
     const char* who = "kde_undist_depth_batch";
     KDE_REQUIRE(h && depth_dev, "%s: null argument", who);
-    KDE_REQUIRE(n >= 1 && n <= h->max_batch, "%s: n=%d outside 1..max_batch=%d", who, n, h->max_batch);
-    KDE_REQUIRE(depth_format_ok(depth_format), "%s: the unknown depth format %d", who, depth_format);
-    KDE_REQUIRE(reinterpret_cast<uintptr_t>(depth_dev) % depth_element(depth_format) == 0, "%s: depth_dev is not %d-byte aligned", who,
-                (int)depth_element(depth_format));
-    KDE_REQUIRE(depth_format_ok(out_format), "%s: the unknown output format %d", who, out_format);
-    KDE_REQUIRE(reinterpret_cast<uintptr_t>(out_dev) % depth_element(out_format) == 0, "%s: out_dev is not %d-byte aligned", who,
-                (int)depth_element(out_format));
+    KDE_TRY(check_batch_n(who, n, h->max_batch));
+    KDE_TRY(check_depth_in(who, depth_dev, depth_format));
+    KDE_TRY(check_depth_out(who, out_dev, out_format));
     KDE_REQUIRE(h->calibrated, "%s: kde_undist_set_calibration was not called", who);
-    KDE_ON_DEVICE(h, who);
-    if (h->device < 0) return fail(KDE_ERR_HIP, "%s: the handle was created on a host without a device", who);
+    KDE_TRY(check_has_device(who, h->device));
     UndistLaunch a = launch_of(h, n);
     a.depth = depth_dev;
     a.depth_format = depth_format;
-    a.out = out_dev ? out_dev : h->depth.p;
+    a.out = h->stage.written(out_dev);
     a.out_format = out_format;
     a.filled = h->filled.p;
     KDE_TRY(launch_undist_depth(a, as_stream(stream)));
-    h->n_last = n;
-    h->format_last = out_format;
-    h->out_last = a.out;
+    h->stage.finished(n, out_format, a.out);
     return KDE_OK;
 }
 
-extern "C" int kde_undist_depth_device(kde_undist* h, void** out)
-{
-    KDE_REQUIRE(h && out, "kde_undist_depth_device: null argument");
-    KDE_REQUIRE(h->n_last > 0, "kde_undist_depth_device: kde_undist_depth_batch was not called");
-    *out = h->out_last;
-    return KDE_OK;
-}
-
-extern "C" int kde_undist_depth_host(kde_undist* h, void* stream, const void** out)
-{
-    const char* who = "kde_undist_depth_host";
-    KDE_REQUIRE(h && out, "%s: null argument", who);
-    KDE_REQUIRE(h->n_last > 0, "%s: kde_undist_depth_batch was not called", who);
-    KDE_ON_DEVICE(h, who);
-    const size_t px = (size_t)h->out_w * h->out_h;
-    KDE_TRY(h->depth_host.ensure((size_t)h->max_batch * px));
-    hipStream_t s = as_stream(stream);
-    KDE_HIP_TRY(hipMemcpyAsync(h->depth_host.p, h->out_last, (size_t)h->n_last * px * depth_element(h->format_last), hipMemcpyDeviceToHost, s));
-    KDE_HIP_TRY(hipStreamSynchronize(s));
-    *out = h->depth_host.p;
-    return KDE_OK;
-}
-
-extern "C" int kde_undist_filled_device(kde_undist* h, uint32_t** out)
-{
-    KDE_REQUIRE(h && out, "kde_undist_filled_device: null argument");
-    KDE_REQUIRE(h->n_last > 0, "kde_undist_filled_device: kde_undist_depth_batch was not called");
-    *out = h->filled.p;
-    return KDE_OK;
-}
-
-extern "C" int kde_undist_filled_host(kde_undist* h, void* stream, const uint32_t** out)
-{
-    KDE_REQUIRE(h && out, "kde_undist_filled_host: null argument");
-    KDE_REQUIRE(h->n_last > 0, "kde_undist_filled_host: kde_undist_depth_batch was not called");
-    return host_mirror("kde_undist_filled_host", h->device, h->filled.p, (size_t)h->n_last, (size_t)h->max_batch, h->filled_host,
-                       as_stream(stream), out);
-}
+KDE_STAGE_DEPTH_GETTERS(kde_undist_depth_device, kde_undist_depth_host, kde_undist, "kde_undist_depth_batch", (size_t)h->out_w * h->out_h)
+KDE_STAGE_COUNT_GETTERS(kde_undist_filled_device, kde_undist_filled_host, kde_undist, "kde_undist_depth_batch", h->filled.p, h->filled_host)
 
 // the map of the calibration in force: computed by U3 on `stream` at the first request after kde_undist_set_calibration
 extern "C" int kde_undist_map_device(kde_undist* h, void* stream, const float** out)
@@ -201,8 +149,7 @@ extern "C" int kde_undist_map_device(kde_undist* h, void* stream, const float** 
     const char* who = "kde_undist_map_device";
     KDE_REQUIRE(h && out, "%s: null argument", who);
     KDE_REQUIRE(h->calibrated, "%s: kde_undist_set_calibration was not called", who);
-    KDE_ON_DEVICE(h, who);
-    if (h->device < 0) return fail(KDE_ERR_HIP, "%s: the handle was created on a host without a device", who);
+    KDE_TRY(check_has_device(who, h->device));
     if (!h->map_valid) {
         KDE_TRY(launch_undist_map(launch_of(h, 1), h->map.p, as_stream(stream)));
         h->map_valid = true;

@@ -18,6 +18,39 @@ __host__ __device__ inline uint16_t depth_to_u16(float z)
     return (r >= 1.0f && r <= 65535.0f) ? (uint16_t)r : (uint16_t)0;
 }
 
+// ---- depth frames of either format, guide colours, counts (reg, undist, upsample, holefill kernels) -----------------------
+// Element `at` of a depth frame that holds floats (is_f32) or the sensor's uint16, widened by (float)u: exact
+__device__ __forceinline__ float load_depth(const char* frame, bool is_f32, size_t at)
+{
+    return is_f32 ? reinterpret_cast<const float*>(frame)[at] : (float)reinterpret_cast<const uint16_t*>(frame)[at];
+}
+
+__device__ __forceinline__ void store_depth(char* frame, bool is_f32, size_t at, float z)
+{
+    if (is_f32) reinterpret_cast<float*>(frame)[at] = z;
+    else reinterpret_cast<uint16_t*>(frame)[at] = depth_to_u16(z);
+}
+
+// a packed BGR pixel as b | g << 8 | r << 16: |db| + |dg| + |dr| of two of them is one v_sad_u8
+__device__ __forceinline__ uint32_t pack_bgr(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16); }
+
+// The sum of v over a workgroup of 256 threads, in two steps so that only the threads that want it read it: the sums of the
+// four waves meet in part[4] (LDS nobody else uses) behind one barrier; block_sum_u32(part) is then their sum.  An integer
+// sum: the same in any order.  (Where the compiler's code for a kernel moved with them, that kernel spells the steps out.)
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
+{
+#pragma unroll
+    for (unsigned off = 32; off >= 1; off >>= 1) v += (uint32_t)__shfl_xor((int)v, (int)off, 64);
+    return v;
+}
+__device__ __forceinline__ void block_partials_u32(uint32_t v, uint32_t* part)
+{
+    v = wave_sum_u32(v);
+    if ((threadIdx.x & 63u) == 0) part[threadIdx.x >> 6] = v;
+    __syncthreads();
+}
+__device__ __forceinline__ uint32_t block_sum_u32(const uint32_t* part) { return (part[0] + part[1]) + (part[2] + part[3]); }
+
 // sqrtf() of an integer-valued float in [0, 2^24): v_rsq_f32 estimate, one Heron step on the exact fma residual.
 // The library sqrtf() spends 14 instructions (denormal scaling, two +-1 ulp probes, class test) to be correctly
 // rounded for every float; on this domain 6 are enough -- tests/test_gpu_dasp_ers.py checks ALL 2^24 arguments

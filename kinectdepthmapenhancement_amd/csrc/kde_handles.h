@@ -101,6 +101,8 @@ inline int superpixel_geometry(int width, int height, int rows, int cols, int mi
 
 }  // namespace kde
 
+#include "kde_depth_stage.h"   // the depth-in / depth-out stages: what their four handles and entry points share
+
 using namespace kde;
 
 // =====================================================================================================

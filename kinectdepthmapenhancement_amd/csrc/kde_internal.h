@@ -62,6 +62,13 @@ constexpr size_t kCacheBytes = (size_t)256 << 20;   // Infinity Cache: calls tha
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
+// A depth frame is KDE_DEPTH_F32 or KDE_DEPTH_U16 (the sensor's millimetres, 0 = invalid): the one statement of the two formats for
+// the host code and the launchers (kde_depth_stage.h holds the rest of what the depth-in / depth-out stages share)
+inline bool depth_format_ok(int f) { return f == KDE_DEPTH_F32 || f == KDE_DEPTH_U16; }
+__host__ __device__ inline size_t depth_element(int f) { return f == KDE_DEPTH_U16 ? sizeof(uint16_t) : sizeof(float); }
+// range[k] of a colour guide, k = |db| + |dg| + |dr| = 0 .. 765 (GuidedDepthUpsampling, DepthHoleFilling)
+constexpr int kColourRange = 766;
+
 // Device buffer with RAII; never throws.
 template <typename T>
 struct DevBuf {
@@ -278,7 +285,6 @@ int launch_undist_depth(const UndistLaunch& a, hipStream_t s);          // 2 ker
 int launch_undist_map(const UndistLaunch& a, float2* map, hipStream_t s);   // map [oh][ow] of (us, vs)
 
 // GuidedDepthUpsampling (upsample_kernels.hip): low-resolution depth to the size of its colour image, a gather
-constexpr int kUpsampleRange = 766;                // range[k], k = |db| + |dg| + |dr| = 0 .. 765
 constexpr int kUpsampleMaxRadius = 4;
 constexpr int kUpsampleTileW = 32, kUpsampleTileH = 8;     // output pixels of a tile
 constexpr int kUpsampleTilesPerGroup = 4;          // consecutive tiles (raster order) of one workgroup
@@ -300,7 +306,7 @@ struct UpsampleLaunch {
     int out_format;                                // KDE_DEPTH_*
     const int* gx_of;                              // [sw]: the output column that is source column qx
     const int* gy_of;                              // [sh]
-    const float* range;                            // [kUpsampleRange]
+    const float* range;                            // [kColourRange]
     uint32_t* partial;                             // [n][upsample_groups(ow, oh)]: the count of each workgroup
     uint32_t* filled;                              // [n]
 };
@@ -308,7 +314,6 @@ unsigned upsample_groups(int ow, int oh);                     // workgroups per 
 int launch_upsample(const UpsampleLaunch& a, hipStream_t s);  // 2 kernels: the upsampling, filled = the sum of its counts
 
 // DepthHoleFilling (holefill_kernels.hip): holes filled from their valid neighbours under a colour guide, pass by pass
-constexpr int kHolefillRange = 766;                // range[k], k = |db| + |dg| + |dr| = 0 .. 765
 constexpr int kHolefillMaxRadius = 3;
 constexpr int kHolefillMaxIterations = 64;
 constexpr int kHolefillMaxFuse = 4;                // passes one launch performs in LDS, at the most
@@ -330,7 +335,7 @@ struct HolefillLaunch {
     float* state[2];                               // [n][h][w] each: the state between two launches
     uint8_t* pass;                                 // [n][h][w]: pass_of, in place between launches and the result
     const float* space;                            // [(2 radius + 1)^2]
-    const float* range;                            // [kHolefillRange]
+    const float* range;                            // [kColourRange]
     uint32_t* partial;                             // [n][holefill_groups(w, h)][2]: the two counts of each workgroup
     uint32_t* filled;                              // [n]
     uint32_t* remaining;                           // [n]

@@ -138,7 +138,7 @@ __device__ __forceinline__ float4 load_quad(const char* frame, int format, unsig
 __device__ __forceinline__ float load_element(const char* frame, int format, unsigned p, unsigned px)
 {
     if (p >= px) return NAN;                                // no range admits it
-    return format == KDE_DEPTH_F32 ? reinterpret_cast<const float*>(frame)[p] : (float)reinterpret_cast<const uint16_t*>(frame)[p];
+    return load_depth(frame, format == KDE_DEPTH_F32, p);
 }
 
 // R0: the grid of R2; every key of the frames in use becomes kEmpty (a thread its octet, two 16-byte stores)
@@ -279,8 +279,7 @@ __global__ __launch_bounds__(kThreads) void reg_gather_kernel(RegLaunch L, const
             const Projected t = project((float)u, (float)v, z[k], L);
             unsigned iu, iv;
             if (t.ok && point_target(t, L, iu, iv)) {
-                const uint8_t* s = img + ((size_t)iv * (unsigned)L.wc + iu) * 3;
-                c[k] = (uint32_t)s[0] | ((uint32_t)s[1] << 8) | ((uint32_t)s[2] << 16);
+                c[k] = pack_bgr(img + ((size_t)iv * (unsigned)L.wc + iu) * 3);
             }
         }
     }
@@ -309,8 +308,6 @@ __global__ __launch_bounds__(kThreads) void reg_gather_kernel(RegLaunch L, const
         }
     }
 }
-
-inline size_t depth_element(int format) { return format == KDE_DEPTH_U16 ? sizeof(uint16_t) : sizeof(float); }
 
 }  // namespace
 

@@ -135,14 +135,6 @@ __device__ __forceinline__ uint32_t color_pixel(const UndistLaunch& L, const uin
     return c;
 }
 
-__device__ __forceinline__ size_t depth_element(int format) { return format == KDE_DEPTH_U16 ? sizeof(uint16_t) : sizeof(float); }
-
-// sample idx of a source frame; uint16 widened by (float)u, exact
-__device__ __forceinline__ float source_depth(const char* frame, int format, size_t idx)
-{
-    return format == KDE_DEPTH_F32 ? reinterpret_cast<const float*>(frame)[idx] : (float)reinterpret_cast<const uint16_t*>(frame)[idx];
-}
-
 // samples idx and idx + 1 of a source frame in one load (an element-aligned pair)
 __device__ __forceinline__ void source_depth_pair(const char* frame, int format, size_t idx, float& a, float& b)
 {
@@ -186,7 +178,7 @@ __device__ __forceinline__ bool depth_pixel(const UndistLaunch& L, const char* f
     z = 0.0f;
     const float fu = rintf(us), fv = rintf(vs);             // ties to even, like depth_to_u16
     if (!(fu >= 0.0f && fu <= lastx && fv >= 0.0f && fv <= lasty)) return false;
-    const float zn = source_depth(frame, L.depth_format, (size_t)fv * (unsigned)L.sw + (size_t)fu);
+    const float zn = load_depth(frame, L.depth_format == KDE_DEPTH_F32, (size_t)fv * (unsigned)L.sw + (size_t)fu);
     if (!(zn > L.z_min && zn < L.z_max)) return false;
     z = zn;
     return true;
@@ -317,8 +309,6 @@ __global__ __launch_bounds__(kThreads) void undist_map_kernel(UndistCalib c, uns
     map[p] = make_float2(us, vs);
 }
 
-inline size_t element_bytes(int format) { return format == KDE_DEPTH_U16 ? sizeof(uint16_t) : sizeof(float); }
-
 }  // namespace
 
 int launch_undist_color(const UndistLaunch& a, const uint8_t* bgr, int bgr_frames, uint8_t* out, hipStream_t s)
@@ -335,7 +325,7 @@ int launch_undist_color(const UndistLaunch& a, const uint8_t* bgr, int bgr_frame
 int launch_undist_depth(const UndistLaunch& a, hipStream_t s)
 {
     const size_t spx = (size_t)a.sw * a.sh, opx = (size_t)a.ow * a.oh;
-    const bool nt = (size_t)a.n * (spx * element_bytes(a.depth_format) + opx * element_bytes(a.out_format)) > kCacheBytes;
+    const bool nt = (size_t)a.n * (spx * depth_element(a.depth_format) + opx * depth_element(a.out_format)) > kCacheBytes;
     const size_t per_block = (size_t)kBlockPixels * kDepthTiles;
     const dim3 grid((unsigned)((opx + per_block - 1) / per_block), (unsigned)a.n), block(kThreads);
     hipLaunchKernelGGL(undist_reset_kernel, dim3((unsigned)((a.n + kThreads - 1) / kThreads)), block, 0, s, a.filled, (unsigned)a.n);

@@ -62,7 +62,7 @@ __global__ __launch_bounds__(kThreads) void upsample_kernel(UpsampleLaunch L)
     const uint8_t* gframe = L.bgr + (L.bgr_frames == 1 ? (size_t)0 : (size_t)frame) * opx * 3;
     char* oframe = static_cast<char*>(L.out) + (size_t)frame * opx * (out_f32 ? sizeof(float) : sizeof(uint16_t));
     const bool vec = (L.ow & 3) == 0 && (reinterpret_cast<uintptr_t>(oframe) & (out_f32 ? 15u : 7u)) == 0;
-    for (int k = tid; k < kUpsampleRange; k += kThreads) s_range[k] = L.range[k];
+    for (int k = tid; k < kColourRange; k += kThreads) s_range[k] = L.range[k];
     const int tiles_x = (L.ow + kTileW - 1) / kTileW, tiles_y = (L.oh + kTileH - 1) / kTileH;
     const int ntiles = tiles_x * tiles_y;
     uint32_t count = 0;
@@ -83,11 +83,10 @@ __global__ __launch_bounds__(kThreads) void upsample_kernel(UpsampleLaunch L)
             uint32_t c = 0u;
             if ((unsigned)qx < (unsigned)L.sw && (unsigned)qy < (unsigned)L.sh) {
                 const size_t at = (size_t)qy * (unsigned)L.sw + (unsigned)qx;
-                const float zz = in_f32 ? reinterpret_cast<const float*>(sframe)[at] : (float)reinterpret_cast<const uint16_t*>(sframe)[at];
+                const float zz = load_depth(sframe, in_f32, at);
                 if (zz > L.z_min && zz < L.z_max) {         // a NaN fails; an absent tap needs no colour
                     z = zz;
-                    const uint8_t* p = gframe + ((size_t)L.gy_of[qy] * (unsigned)L.ow + (unsigned)L.gx_of[qx]) * 3;
-                    c = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
+                    c = pack_bgr(gframe + ((size_t)L.gy_of[qy] * (unsigned)L.ow + (unsigned)L.gx_of[qx]) * 3);
                 }
             }
             s_z[wy * kWinW + wx] = z;
@@ -103,8 +102,7 @@ __global__ __launch_bounds__(kThreads) void upsample_kernel(UpsampleLaunch L)
             float wxs[T];
 #pragma unroll
             for (int a = 0; a < T; a++) wxs[a] = tent(x0 - R + 1 + a, u, (float)R);
-            const uint8_t* p = gframe + ((size_t)j * (unsigned)L.ow + (unsigned)i) * 3;
-            const uint32_t own = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
+            const uint32_t own = pack_bgr(gframe + ((size_t)j * (unsigned)L.ow + (unsigned)i) * 3);
             const int base = (y0 - yf) * kWinW + (x0 - xf);
             const float* zt = s_z + base;
             const uint32_t* ct = s_c + base;
@@ -177,16 +175,11 @@ __global__ __launch_bounds__(kThreads) void upsample_kernel(UpsampleLaunch L)
                 }
             }
         } else if (active) {
-            const size_t at = (size_t)j * (unsigned)L.ow + (unsigned)i;
-            if (out_f32) reinterpret_cast<float*>(oframe)[at] = result;
-            else reinterpret_cast<uint16_t*>(oframe)[at] = depth_to_u16(result);
+            store_depth(oframe, out_f32, (size_t)j * (unsigned)L.ow + (unsigned)i, result);
         }
     }
-#pragma unroll
-    for (unsigned off = 32; off >= 1; off >>= 1) count += (uint32_t)__shfl_xor((int)count, (int)off, 64);
-    if ((tid & 63) == 0) s_count[tid >> 6] = count;
-    __syncthreads();
-    if (tid == 0) L.partial[(size_t)frame * gridDim.x + blockIdx.x] = (s_count[0] + s_count[1]) + (s_count[2] + s_count[3]);
+    block_partials_u32(count, s_count);
+    if (tid == 0) L.partial[(size_t)frame * gridDim.x + blockIdx.x] = block_sum_u32(s_count);
 }
 
 // G2: grid n, block 256

@@ -967,50 +967,41 @@ class PointCloudXYZRGB(_Handle):
         return [raw[int(offsets[f]):int(offsets[f + 1])] for f in range(self._n)]
 
 
-class DepthRegistration(_Handle):
-    """What Kinect::InitAllData (Kinect.cpp:71-75) asks OpenNI for, on the device (kde_reg_*): depth frames warped into the
-    colour camera's view, so that depth pixel (x, y) and colour pixel (x, y) look along the same ray, as every other class
-    here assumes.  depth_size and color_size are (width, height); params is a RegParams (z_min, z_max, max_splat) or None
-    for the defaults (0, FLT_MAX, point mode).  The rule is stated in include/kde_hip.h: a scatter through a z-buffer, the
-    nearest source pixel wins, deterministic to the bit; cx and cy are kept as floats, there is no lens distortion."""
-    _destroy = "kde_reg_destroy"
-    _handle_type = _native.RegHandle
+class _DepthStage(_Handle):
+    """What the depth-in / depth-out stages share (csrc/kde_depth_stage.h in the library): n depth frames in as float32 or
+    uint16, n frames out in either format, the results of the last batch call.  A subclass names its C prefix and its
+    parameter struct, sets self._out_hw = (height, width) of an output frame in __init__ and records every batch call
+    with _finished()."""
+    _prefix = None                  # "kde_reg_", ...: default_params and the getters are this plus their name
+    _params_type = None
 
-    def __init__(self, depth_size, color_size, max_batch: int = 1, params: Optional["_native.RegParams"] = None):
+    def __init__(self, max_batch: int):
         super().__init__()
-        (self.depth_width, self.depth_height), (self.color_width, self.color_height) = depth_size, color_size
         self.max_batch = max_batch
         self._n, self._fmt = 0, _native.KDE_DEPTH_F32
-        check(lib().kde_reg_create(C.byref(self._h), self.depth_width, self.depth_height, self.color_width, self.color_height,
-                                   max_batch, None if params is None else C.byref(params)))
 
-    @staticmethod
-    def default_params() -> "_native.RegParams":
-        p = _native.RegParams()
-        check(lib().kde_reg_default_params(C.byref(p)))
+    @classmethod
+    def default_params(cls):
+        p = cls._params_type()
+        check(getattr(lib(), cls._prefix + "default_params")(C.byref(p)))
         return p
 
-    def set_calibration(self, Kd, Kc, R, t) -> None:
-        """Kd, Kc, R: 3 x 3 (row-major); t: 3 values in millimetres; P_colour = R * P_depth + t"""
-        kd, kc, r = _K9(Kd), _K9(Kc), _K9(R)
-        tt = np.ascontiguousarray(np.asarray(t, np.float64).reshape(3))
-        check(lib().kde_reg_set_calibration(self._h, kd.ctypes.data, kc.ctypes.data, r.ctypes.data, tt.ctypes.data))
+    def _fn(self, name: str):
+        return getattr(lib(), self._prefix + name)
 
-    def _depth_format(self, depth: torch.Tensor):
+    @staticmethod
+    def _check_depth(depth: torch.Tensor, height: int, width: int):
+        """(n, KDE_DEPTH_*) of an input depth tensor [n,height,width]"""
         if not isinstance(depth, torch.Tensor) or not depth.is_cuda:
             raise TypeError("depth: expected a CUDA tensor")
-        if depth.dim() != 3 or tuple(depth.shape[1:]) != (self.depth_height, self.depth_width) or not depth.is_contiguous() or \
+        if depth.dim() != 3 or tuple(depth.shape[1:]) != (height, width) or not depth.is_contiguous() or \
                 depth.dtype not in (torch.float32, torch.int16, _U16):
-            raise ValueError(f"depth: expected contiguous float32 / uint16 [n,{self.depth_height},{self.depth_width}], got "
+            raise ValueError(f"depth: expected contiguous float32 / uint16 [n,{height},{width}], got "
                              f"{depth.dtype} {tuple(depth.shape)}")
         return depth.shape[0], (_native.KDE_DEPTH_F32 if depth.dtype == torch.float32 else _native.KDE_DEPTH_U16)
 
-    def register(self, depth: torch.Tensor, out: Optional[torch.Tensor] = None, out_format=torch.float32) -> torch.Tensor:
-        """depth: [n,Hd,Wd] float32, or uint16 / int16 holding the sensor's uint16.  out: [n,Hc,Wc] float32 or uint16 / int16
-        (its dtype is the output format), or None for the object-owned buffer in out_format (torch.float32, torch.uint16 or
-        torch.int16).  Returns the registered frames (0 where no source pixel came).  Asynchronous on torch's current stream;
-        no allocation, copy or synchronisation on the device."""
-        n, fmt = self._depth_format(depth)
+    def _out_format(self, out: Optional[torch.Tensor], out_format, n: int) -> int:
+        """KDE_DEPTH_* of a batch call's output: the dtype of `out` [n, output frame], or out_format where out is None"""
         dt = out.dtype if isinstance(out, torch.Tensor) else out_format
         if dt == torch.float32:
             ofmt = _native.KDE_DEPTH_F32
@@ -1019,47 +1010,92 @@ class DepthRegistration(_Handle):
         else:
             raise ValueError(f"out_format: expected torch.float32 or torch.uint16, got {dt}")
         if out is not None:
-            _req(out, dt, (n, self.color_height, self.color_width), "out")
-        check(lib().kde_reg_register_batch(self._h, n, depth.data_ptr(), fmt, ofmt, _ptr(out), _stream()))
+            _req(out, dt, (n,) + self._out_hw, "out")
+        return ofmt
+
+    @staticmethod
+    def _check_guide(bgr: torch.Tensor, n: int, height: int, width: int) -> None:
+        if not isinstance(bgr, torch.Tensor) or bgr.dim() != 4 or bgr.shape[0] not in (1, n):
+            raise ValueError(f"bgr: expected [1 or {n},{height},{width},3] uint8")
+        _req(bgr, torch.uint8, (bgr.shape[0], height, width, 3), "bgr")
+
+    def _finished(self, n: int, ofmt: int, out: Optional[torch.Tensor]) -> torch.Tensor:
         self._n, self._fmt = n, ofmt
         return out if out is not None else self.depth_device()
 
     def depth_device(self) -> torch.Tensor:
-        """the frames of the last register(): `out` of that call or the object-owned buffer, [n,Hc,Wc] float32, or int16
+        """the frames of the last batch call: `out` of that call or the object-owned buffer, [n,Ho,Wo] float32, or int16
         holding the uint16 bits (`.cpu().numpy().view(numpy.uint16)`)"""
         p = C.c_void_p()
-        check(lib().kde_reg_depth_device(self._h, C.byref(p)))
+        check(self._fn("depth_device")(self._h, C.byref(p)))
+        h, w = self._out_hw
         if self._fmt == _native.KDE_DEPTH_F32:
-            return _view(p.value, (self._n, self.color_height, self.color_width), torch.float32, self)
-        return _view(p.value, (self._n, self.color_height, self.color_width * 2), torch.uint8, self).view(torch.int16)
+            return _view(p.value, (self._n, h, w), torch.float32, self)
+        return _view(p.value, (self._n, h, w * 2), torch.uint8, self).view(torch.int16)
 
     def depth_host(self) -> np.ndarray:
         """the same as a numpy array, float32 or uint16; synchronises torch's current stream"""
         p = C.c_void_p()
-        check(lib().kde_reg_depth_host(self._h, _stream(), C.byref(p)))
+        check(self._fn("depth_host")(self._h, _stream(), C.byref(p)))
         ctype, dtype = (C.c_float, np.float32) if self._fmt == _native.KDE_DEPTH_F32 else (C.c_uint16, np.uint16)
-        shape = (self._n, self.color_height, self.color_width)
-        return np.ctypeslib.as_array(C.cast(p, C.POINTER(ctype)), shape=shape).astype(dtype, copy=True)
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(ctype)), shape=(self._n,) + self._out_hw).astype(dtype, copy=True)
+
+    def _count_host(self, fn) -> np.ndarray:
+        p = C.c_void_p()
+        check(fn(self._h, _stream(), C.byref(p)))
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint32)), shape=(self._n,)).copy()
+
+    def _count_device(self, fn) -> torch.Tensor:
+        p = C.c_void_p()
+        check(fn(self._h, C.byref(p)))
+        return _view(p.value, (self._n, 4), torch.uint8, self)
 
     def filled(self) -> np.ndarray:
-        """the number of target pixels reached per frame of the last register(), uint32 [n]; synchronises torch's current stream"""
-        p = C.c_void_p()
-        check(lib().kde_reg_filled_host(self._h, _stream(), C.byref(p)))
-        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint32)), shape=(self._n,)).copy()
+        """the number of pixels per frame the last batch call gave a depth, uint32 [n]; synchronises torch's current stream"""
+        return self._count_host(self._fn("filled_host"))
 
     def filled_device(self) -> torch.Tensor:
         """the same on the device, as raw bytes [n, 4] (uint32), a view of the object-owned buffer"""
-        p = C.c_void_p()
-        check(lib().kde_reg_filled_device(self._h, C.byref(p)))
-        return _view(p.value, (self._n, 4), torch.uint8, self)
+        return self._count_device(self._fn("filled_device"))
+
+
+class DepthRegistration(_DepthStage):
+    """What Kinect::InitAllData (Kinect.cpp:71-75) asks OpenNI for, on the device (kde_reg_*): depth frames warped into the
+    colour camera's view, so that depth pixel (x, y) and colour pixel (x, y) look along the same ray, as every other class
+    here assumes.  depth_size and color_size are (width, height); params is a RegParams (z_min, z_max, max_splat) or None
+    for the defaults (0, FLT_MAX, point mode).  The rule is stated in include/kde_hip.h: a scatter through a z-buffer, the
+    nearest source pixel wins, deterministic to the bit; cx and cy are kept as floats, there is no lens distortion."""
+    _destroy, _prefix = "kde_reg_destroy", "kde_reg_"
+    _handle_type, _params_type = _native.RegHandle, _native.RegParams
+
+    def __init__(self, depth_size, color_size, max_batch: int = 1, params: Optional["_native.RegParams"] = None):
+        super().__init__(max_batch)
+        (self.depth_width, self.depth_height), (self.color_width, self.color_height) = depth_size, color_size
+        self._out_hw = (self.color_height, self.color_width)
+        check(lib().kde_reg_create(C.byref(self._h), self.depth_width, self.depth_height, self.color_width, self.color_height,
+                                   max_batch, None if params is None else C.byref(params)))
+
+    def set_calibration(self, Kd, Kc, R, t) -> None:
+        """Kd, Kc, R: 3 x 3 (row-major); t: 3 values in millimetres; P_colour = R * P_depth + t"""
+        kd, kc, r = _K9(Kd), _K9(Kc), _K9(R)
+        tt = np.ascontiguousarray(np.asarray(t, np.float64).reshape(3))
+        check(lib().kde_reg_set_calibration(self._h, kd.ctypes.data, kc.ctypes.data, r.ctypes.data, tt.ctypes.data))
+
+    def register(self, depth: torch.Tensor, out: Optional[torch.Tensor] = None, out_format=torch.float32) -> torch.Tensor:
+        """depth: [n,Hd,Wd] float32, or uint16 / int16 holding the sensor's uint16.  out: [n,Hc,Wc] float32 or uint16 / int16
+        (its dtype is the output format), or None for the object-owned buffer in out_format (torch.float32, torch.uint16 or
+        torch.int16).  Returns the registered frames (0 where no source pixel came).  Asynchronous on torch's current stream;
+        no allocation, copy or synchronisation on the device."""
+        n, fmt = self._check_depth(depth, self.depth_height, self.depth_width)
+        ofmt = self._out_format(out, out_format, n)
+        check(lib().kde_reg_register_batch(self._h, n, depth.data_ptr(), fmt, ofmt, _ptr(out), _stream()))
+        return self._finished(n, ofmt, out)
 
     def color_to_depth(self, depth: torch.Tensor, bgr: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """the companion gather: bgr uint8 [n,Hc,Wc,3] or [1,Hc,Wc,3] as the depth camera sees it, uint8 [n,Hd,Wd,3]: the colour
         at the point-mode target of each valid depth pixel, (0, 0, 0) elsewhere.  No occlusion test."""
-        n, fmt = self._depth_format(depth)
-        if not isinstance(bgr, torch.Tensor) or bgr.dim() != 4 or bgr.shape[0] not in (1, n):
-            raise ValueError(f"bgr: expected [1 or {n},{self.color_height},{self.color_width},3] uint8")
-        _req(bgr, torch.uint8, (bgr.shape[0], self.color_height, self.color_width, 3), "bgr")
+        n, fmt = self._check_depth(depth, self.depth_height, self.depth_width)
+        self._check_guide(bgr, n, self.color_height, self.color_width)
         if out is None:
             out = torch.empty((n, self.depth_height, self.depth_width, 3), dtype=torch.uint8, device=depth.device)
         else:
@@ -1069,30 +1105,23 @@ class DepthRegistration(_Handle):
         return out
 
 
-class LensUndistortion(_Handle):
+class LensUndistortion(_DepthStage):
     """Frames of a camera with lens distortion resampled into the pinhole view every other class here assumes, on the device
     (kde_undist_*): OpenCV's rational model (k1, k2, p1, p2, k3, k4, k5, k6; zeros for k4..k6 give Brown-Conrady), no
     rectifying rotation.  src_size and out_size are (width, height); params is an UndistParams (z_min, z_max, depth_interp,
     max_gap) or None for the defaults (0, FLT_MAX, nearest).  The rule is stated in include/kde_hip.h: colour is bilinear
     with (0, 0, 0) outside the source, depth is the nearest valid sample or, with depth_interp 1, bilinear where the four
     taps are valid and within max_gap of each other; deterministic to the bit."""
-    _destroy = "kde_undist_destroy"
-    _handle_type = _native.UndistHandle
+    _destroy, _prefix = "kde_undist_destroy", "kde_undist_"
+    _handle_type, _params_type = _native.UndistHandle, _native.UndistParams
 
     def __init__(self, src_size, out_size=None, max_batch: int = 1, params: Optional["_native.UndistParams"] = None):
-        super().__init__()
+        super().__init__(max_batch)
         self.src_width, self.src_height = src_size
         self.out_width, self.out_height = out_size if out_size is not None else src_size
-        self.max_batch = max_batch
-        self._n, self._fmt = 0, _native.KDE_DEPTH_F32
+        self._out_hw = (self.out_height, self.out_width)
         check(lib().kde_undist_create(C.byref(self._h), self.src_width, self.src_height, self.out_width, self.out_height,
                                       max_batch, None if params is None else C.byref(params)))
-
-    @staticmethod
-    def default_params() -> "_native.UndistParams":
-        p = _native.UndistParams()
-        check(lib().kde_undist_default_params(C.byref(p)))
-        return p
 
     def set_calibration(self, K, dist, K_new=None) -> None:
         """K, K_new: 3 x 3 (row-major), K_new None for K; dist: k1, k2, p1, p2, k3[, k4, k5, k6] (4, 5 or 8 values as OpenCV
@@ -1127,56 +1156,10 @@ class LensUndistortion(_Handle):
         (its dtype is the output format), or None for the object-owned buffer in out_format (torch.float32, torch.uint16 or
         torch.int16).  Returns the undistorted frames (0 where a pixel got no depth).  Asynchronous on torch's current stream;
         no allocation, copy or synchronisation on the device."""
-        if not isinstance(depth, torch.Tensor) or not depth.is_cuda:
-            raise TypeError("depth: expected a CUDA tensor")
-        if depth.dim() != 3 or tuple(depth.shape[1:]) != (self.src_height, self.src_width) or not depth.is_contiguous() or \
-                depth.dtype not in (torch.float32, torch.int16, _U16):
-            raise ValueError(f"depth: expected contiguous float32 / uint16 [n,{self.src_height},{self.src_width}], got "
-                             f"{depth.dtype} {tuple(depth.shape)}")
-        n = depth.shape[0]
-        fmt = _native.KDE_DEPTH_F32 if depth.dtype == torch.float32 else _native.KDE_DEPTH_U16
-        dt = out.dtype if isinstance(out, torch.Tensor) else out_format
-        if dt == torch.float32:
-            ofmt = _native.KDE_DEPTH_F32
-        elif dt is not None and dt in (torch.int16, _U16):
-            ofmt = _native.KDE_DEPTH_U16
-        else:
-            raise ValueError(f"out_format: expected torch.float32 or torch.uint16, got {dt}")
-        if out is not None:
-            _req(out, dt, (n, self.out_height, self.out_width), "out")
+        n, fmt = self._check_depth(depth, self.src_height, self.src_width)
+        ofmt = self._out_format(out, out_format, n)
         check(lib().kde_undist_depth_batch(self._h, n, depth.data_ptr(), fmt, ofmt, _ptr(out), _stream()))
-        self._n, self._fmt = n, ofmt
-        return out if out is not None else self.depth_device()
-
-    def depth_device(self) -> torch.Tensor:
-        """the frames of the last depth(): `out` of that call or the object-owned buffer, [n,Ho,Wo] float32, or int16 holding
-        the uint16 bits (`.cpu().numpy().view(numpy.uint16)`)"""
-        p = C.c_void_p()
-        check(lib().kde_undist_depth_device(self._h, C.byref(p)))
-        if self._fmt == _native.KDE_DEPTH_F32:
-            return _view(p.value, (self._n, self.out_height, self.out_width), torch.float32, self)
-        return _view(p.value, (self._n, self.out_height, self.out_width * 2), torch.uint8, self).view(torch.int16)
-
-    def depth_host(self) -> np.ndarray:
-        """the same as a numpy array, float32 or uint16; synchronises torch's current stream"""
-        p = C.c_void_p()
-        check(lib().kde_undist_depth_host(self._h, _stream(), C.byref(p)))
-        ctype, dtype = (C.c_float, np.float32) if self._fmt == _native.KDE_DEPTH_F32 else (C.c_uint16, np.uint16)
-        shape = (self._n, self.out_height, self.out_width)
-        return np.ctypeslib.as_array(C.cast(p, C.POINTER(ctype)), shape=shape).astype(dtype, copy=True)
-
-    def filled(self) -> np.ndarray:
-        """the number of output pixels that got a depth per frame of the last depth(), uint32 [n]; synchronises torch's
-        current stream"""
-        p = C.c_void_p()
-        check(lib().kde_undist_filled_host(self._h, _stream(), C.byref(p)))
-        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint32)), shape=(self._n,)).copy()
-
-    def filled_device(self) -> torch.Tensor:
-        """the same on the device, as raw bytes [n, 4] (uint32), a view of the object-owned buffer"""
-        p = C.c_void_p()
-        check(lib().kde_undist_filled_device(self._h, C.byref(p)))
-        return _view(p.value, (self._n, 4), torch.uint8, self)
+        return self._finished(n, ofmt, out)
 
     def map(self) -> torch.Tensor:
         """(us, vs) of every output pixel, float32 [Ho,Wo,2]: the source point it shows, OpenCV's initUndistortRectifyMap
@@ -1187,30 +1170,23 @@ class LensUndistortion(_Handle):
         return _view(p.value, (self.out_height, self.out_width, 2), torch.float32, self)
 
 
-class GuidedDepthUpsampling(_Handle):
+class GuidedDepthUpsampling(_DepthStage):
     """A low-resolution depth frame brought to the size of its colour image on the device (kde_upsample_*): joint bilateral
     upsampling, low-resolution samples weighted by a tent of radius `radius` around the output pixel and by the resemblance
     of the guide colour at the output pixel to the guide colour at the sample.  src_size and out_size are (width, height),
     out_size no smaller than src_size; params is an UpsampleParams (radius, sigma_color, max_gap, z_min, z_max) or None for the
     defaults (2, 30, no guard, every finite positive depth).  The rule is stated in include/kde_hip.h; deterministic to the
     bit."""
-    _destroy = "kde_upsample_destroy"
-    _handle_type = _native.UpsampleHandle
+    _destroy, _prefix = "kde_upsample_destroy", "kde_upsample_"
+    _handle_type, _params_type = _native.UpsampleHandle, _native.UpsampleParams
 
     def __init__(self, src_size, out_size, max_batch: int = 1, params: Optional["_native.UpsampleParams"] = None):
-        super().__init__()
+        super().__init__(max_batch)
         self.src_width, self.src_height = src_size
         self.out_width, self.out_height = out_size
-        self.max_batch = max_batch
-        self._n, self._fmt = 0, _native.KDE_DEPTH_F32
+        self._out_hw = (self.out_height, self.out_width)
         check(lib().kde_upsample_create(C.byref(self._h), self.src_width, self.src_height, self.out_width, self.out_height,
                                         max_batch, None if params is None else C.byref(params)))
-
-    @staticmethod
-    def default_params() -> "_native.UpsampleParams":
-        p = _native.UpsampleParams()
-        check(lib().kde_upsample_default_params(C.byref(p)))
-        return p
 
     def range_table(self) -> np.ndarray:
         """range[k] for k = |db| + |dg| + |dr| = 0 .. 765 as the kernel reads it, float32 [766]; needs no device"""
@@ -1225,84 +1201,29 @@ class GuidedDepthUpsampling(_Handle):
         format), or None for the object-owned buffer in out_format (torch.float32, torch.uint16 or torch.int16).  Returns
         the upsampled frames (0 where a pixel got no depth).  Asynchronous on torch's current stream; no allocation, copy
         or synchronisation on the device."""
-        if not isinstance(depth, torch.Tensor) or not depth.is_cuda:
-            raise TypeError("depth: expected a CUDA tensor")
-        if depth.dim() != 3 or tuple(depth.shape[1:]) != (self.src_height, self.src_width) or not depth.is_contiguous() or \
-                depth.dtype not in (torch.float32, torch.int16, _U16):
-            raise ValueError(f"depth: expected contiguous float32 / uint16 [n,{self.src_height},{self.src_width}], got "
-                             f"{depth.dtype} {tuple(depth.shape)}")
-        n = depth.shape[0]
-        if not isinstance(bgr, torch.Tensor) or bgr.dim() != 4 or bgr.shape[0] not in (1, n):
-            raise ValueError(f"bgr: expected [1 or {n},{self.out_height},{self.out_width},3] uint8")
-        _req(bgr, torch.uint8, (bgr.shape[0], self.out_height, self.out_width, 3), "bgr")
-        fmt = _native.KDE_DEPTH_F32 if depth.dtype == torch.float32 else _native.KDE_DEPTH_U16
-        dt = out.dtype if isinstance(out, torch.Tensor) else out_format
-        if dt == torch.float32:
-            ofmt = _native.KDE_DEPTH_F32
-        elif dt is not None and dt in (torch.int16, _U16):
-            ofmt = _native.KDE_DEPTH_U16
-        else:
-            raise ValueError(f"out_format: expected torch.float32 or torch.uint16, got {dt}")
-        if out is not None:
-            _req(out, dt, (n, self.out_height, self.out_width), "out")
+        n, fmt = self._check_depth(depth, self.src_height, self.src_width)
+        self._check_guide(bgr, n, self.out_height, self.out_width)
+        ofmt = self._out_format(out, out_format, n)
         check(lib().kde_upsample_depth_batch(self._h, n, depth.data_ptr(), fmt, bgr.data_ptr(), bgr.shape[0], ofmt, _ptr(out), _stream()))
-        self._n, self._fmt = n, ofmt
-        return out if out is not None else self.depth_device()
-
-    def depth_device(self) -> torch.Tensor:
-        """the frames of the last upsample(): `out` of that call or the object-owned buffer, [n,Ho,Wo] float32, or int16
-        holding the uint16 bits (`.cpu().numpy().view(numpy.uint16)`)"""
-        p = C.c_void_p()
-        check(lib().kde_upsample_depth_device(self._h, C.byref(p)))
-        if self._fmt == _native.KDE_DEPTH_F32:
-            return _view(p.value, (self._n, self.out_height, self.out_width), torch.float32, self)
-        return _view(p.value, (self._n, self.out_height, self.out_width * 2), torch.uint8, self).view(torch.int16)
-
-    def depth_host(self) -> np.ndarray:
-        """the same as a numpy array, float32 or uint16; synchronises torch's current stream"""
-        p = C.c_void_p()
-        check(lib().kde_upsample_depth_host(self._h, _stream(), C.byref(p)))
-        ctype, dtype = (C.c_float, np.float32) if self._fmt == _native.KDE_DEPTH_F32 else (C.c_uint16, np.uint16)
-        shape = (self._n, self.out_height, self.out_width)
-        return np.ctypeslib.as_array(C.cast(p, C.POINTER(ctype)), shape=shape).astype(dtype, copy=True)
-
-    def filled(self) -> np.ndarray:
-        """the number of output pixels that got a depth per frame of the last upsample(), uint32 [n]; synchronises torch's
-        current stream"""
-        p = C.c_void_p()
-        check(lib().kde_upsample_filled_host(self._h, _stream(), C.byref(p)))
-        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint32)), shape=(self._n,)).copy()
-
-    def filled_device(self) -> torch.Tensor:
-        """the same on the device, as raw bytes [n, 4] (uint32), a view of the object-owned buffer"""
-        p = C.c_void_p()
-        check(lib().kde_upsample_filled_device(self._h, C.byref(p)))
-        return _view(p.value, (self._n, 4), torch.uint8, self)
+        return self._finished(n, ofmt, out)
 
 
-class DepthHoleFilling(_Handle):
+class DepthHoleFilling(_DepthStage):
     """The holes of a depth frame filled on the device under the guide of its colour image (kde_holefill_*): `iterations`
     passes, each of which gives the hole pixels with at least `min_taps` usable neighbours within `radius` the mean of those
     neighbours, weighted by distance and by the resemblance of the guide colour; iterations * radius bounds how far a fill
     reaches.  size is (width, height); params is a HolefillParams (radius, iterations, min_taps, sigma_space, sigma_color,
     max_gap, gap_rule, z_min, z_max, passes_per_launch) or None for the defaults (2, 8, 3, 2, 30, no guard, every finite
     positive depth, the library's passes per launch).  The rule is stated in include/kde_hip.h; deterministic to the bit."""
-    _destroy = "kde_holefill_destroy"
-    _handle_type = _native.HolefillHandle
+    _destroy, _prefix = "kde_holefill_destroy", "kde_holefill_"
+    _handle_type, _params_type = _native.HolefillHandle, _native.HolefillParams
 
     def __init__(self, size, max_batch: int = 1, params: Optional["_native.HolefillParams"] = None):
-        super().__init__()
+        super().__init__(max_batch)
         self.width, self.height = size
-        self.max_batch = max_batch
-        self._n, self._fmt = 0, _native.KDE_DEPTH_F32
+        self._out_hw = (self.height, self.width)
         check(lib().kde_holefill_create(C.byref(self._h), self.width, self.height, max_batch, None if params is None else C.byref(params)))
         self.radius = (self.default_params() if params is None else params).radius
-
-    @staticmethod
-    def default_params() -> "_native.HolefillParams":
-        p = _native.HolefillParams()
-        check(lib().kde_holefill_default_params(C.byref(p)))
-        return p
 
     def space_table(self) -> np.ndarray:
         """space[dy + r][dx + r] as the kernel reads it, float32 [2r + 1, 2r + 1]; needs no device"""
@@ -1331,70 +1252,18 @@ class DepthHoleFilling(_Handle):
         must not overlap depth, so a result returned by fill(..., out=None) goes back in only with an `out` for the new one.  pass_of: uint8 [n,H,W] or None: 0 for an original pixel, p for one filled in pass p, 255 for one that is
         still a hole.  Returns the filled frames (0 where a hole remains).  Asynchronous on torch's current stream; no
         allocation, copy or synchronisation on the device."""
-        if not isinstance(depth, torch.Tensor) or not depth.is_cuda:
-            raise TypeError("depth: expected a CUDA tensor")
-        if depth.dim() != 3 or tuple(depth.shape[1:]) != (self.height, self.width) or not depth.is_contiguous() or \
-                depth.dtype not in (torch.float32, torch.int16, _U16):
-            raise ValueError(f"depth: expected contiguous float32 / uint16 [n,{self.height},{self.width}], got "
-                             f"{depth.dtype} {tuple(depth.shape)}")
-        n = depth.shape[0]
-        if not isinstance(bgr, torch.Tensor) or bgr.dim() != 4 or bgr.shape[0] not in (1, n):
-            raise ValueError(f"bgr: expected [1 or {n},{self.height},{self.width},3] uint8")
-        _req(bgr, torch.uint8, (bgr.shape[0], self.height, self.width, 3), "bgr")
-        fmt = _native.KDE_DEPTH_F32 if depth.dtype == torch.float32 else _native.KDE_DEPTH_U16
-        dt = out.dtype if isinstance(out, torch.Tensor) else out_format
-        if dt == torch.float32:
-            ofmt = _native.KDE_DEPTH_F32
-        elif dt is not None and dt in (torch.int16, _U16):
-            ofmt = _native.KDE_DEPTH_U16
-        else:
-            raise ValueError(f"out_format: expected torch.float32 or torch.uint16, got {dt}")
-        if out is not None:
-            _req(out, dt, (n, self.height, self.width), "out")
+        n, fmt = self._check_depth(depth, self.height, self.width)
+        self._check_guide(bgr, n, self.height, self.width)
+        ofmt = self._out_format(out, out_format, n)
         if pass_of is not None:
             _req(pass_of, torch.uint8, (n, self.height, self.width), "pass_of")
         check(lib().kde_holefill_fill_batch(self._h, n, depth.data_ptr(), fmt, bgr.data_ptr(), bgr.shape[0], ofmt, _ptr(out), _ptr(pass_of),
                                             _stream()))
-        self._n, self._fmt = n, ofmt
-        return out if out is not None else self.depth_device()
-
-    def depth_device(self) -> torch.Tensor:
-        """the frames of the last fill(): `out` of that call or the object-owned buffer, [n,H,W] float32, or int16 holding
-        the uint16 bits (`.cpu().numpy().view(numpy.uint16)`)"""
-        p = C.c_void_p()
-        check(lib().kde_holefill_depth_device(self._h, C.byref(p)))
-        if self._fmt == _native.KDE_DEPTH_F32:
-            return _view(p.value, (self._n, self.height, self.width), torch.float32, self)
-        return _view(p.value, (self._n, self.height, self.width * 2), torch.uint8, self).view(torch.int16)
-
-    def depth_host(self) -> np.ndarray:
-        """the same as a numpy array, float32 or uint16; synchronises torch's current stream"""
-        p = C.c_void_p()
-        check(lib().kde_holefill_depth_host(self._h, _stream(), C.byref(p)))
-        ctype, dtype = (C.c_float, np.float32) if self._fmt == _native.KDE_DEPTH_F32 else (C.c_uint16, np.uint16)
-        return np.ctypeslib.as_array(C.cast(p, C.POINTER(ctype)), shape=(self._n, self.height, self.width)).astype(dtype, copy=True)
-
-    def _count_host(self, fn) -> np.ndarray:
-        p = C.c_void_p()
-        check(fn(self._h, _stream(), C.byref(p)))
-        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint32)), shape=(self._n,)).copy()
-
-    def _count_device(self, fn) -> torch.Tensor:
-        p = C.c_void_p()
-        check(fn(self._h, C.byref(p)))
-        return _view(p.value, (self._n, 4), torch.uint8, self)
-
-    def filled(self) -> np.ndarray:
-        """the number of pixels per frame the last fill() gave a depth, uint32 [n]; synchronises torch's current stream"""
-        return self._count_host(lib().kde_holefill_filled_host)
+        return self._finished(n, ofmt, out)
 
     def remaining(self) -> np.ndarray:
         """the number of pixels per frame that are still holes after the last fill(), uint32 [n]; synchronises"""
         return self._count_host(lib().kde_holefill_remaining_host)
-
-    def filled_device(self) -> torch.Tensor:
-        """filled on the device, as raw bytes [n, 4] (uint32), a view of the object-owned buffer"""
-        return self._count_device(lib().kde_holefill_filled_device)
 
     def remaining_device(self) -> torch.Tensor:
         """remaining on the device, as raw bytes [n, 4] (uint32), a view of the object-owned buffer"""
