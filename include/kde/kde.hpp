@@ -1439,6 +1439,65 @@ public:
     void rangeTable(float (&table_host)[766]) const { check(kde_holefill_range_table(h_, table_host, 766)); }
 };
 
+// extension (no reference counterpart): wrong depth taken away on the device (kde_speckle_*) -- the connected components of a
+// frame under a depth-difference link (within max_diff + rel_diff * the nearer depth, 4- or 8-connected), those smaller than
+// min_size set to 0: flying pixels, speckles, background showing through a registered foreground.  Behind the registration,
+// the undistortion and the upsampling and in front of DepthHoleFilling: invalidate first, then fill.  The rule is stated in
+// kde_hip.h; deterministic to the bit.  filter() is asynchronous on the object's stream and capturable; the *_Host members
+// synchronise.  The count of the shared core is removed[f] here: removed_Device() / removed_Host().
+class DepthSpeckleFilter
+    : public detail::DepthStage<kde_speckle, kde_speckle_params, kde_speckle_default_params, kde_speckle_destroy, kde_speckle_depth_device,
+                                kde_speckle_depth_host, kde_speckle_removed_device, kde_speckle_removed_host> {
+public:
+    DepthSpeckleFilter(int width, int height, int max_batch = 1) { check(kde_speckle_create(&h_, width, height, max_batch, nullptr)); }
+    DepthSpeckleFilter(int width, int height, int max_batch, const kde_speckle_params& params)
+    {
+        check(kde_speckle_create(&h_, width, height, max_batch, &params));
+    }
+
+    // n depth frames back to back; the output format is the type of out_device (nullptr of that type: the object-owned buffer);
+    // out_device may be depth_device itself (in place) and must not overlap it otherwise; labels_device: n frames of int32 (the
+    // smallest raster index of a kept pixel's component, -1 where the output is 0) or nullptr where it is not wanted
+    template <class Depth, class Out>
+    void filter(int n, const Depth* depth_device, Out* out_device, int32_t* labels_device = nullptr)
+    {
+        check(kde_speckle_filter_batch(h_, n, depth_device, format(depth_device), format(out_device), out_device, labels_device, stream_));
+    }
+    // the pixels with a depth that the last filter() set to 0, per frame
+    uint32_t* removed_Device() const { return filled_Device(); }
+    const uint32_t* removed_Host() const { return filled_Host(); }
+    // the components the last filter() kept, per frame
+    uint32_t* components_Device() const
+    {
+        uint32_t* p = nullptr;
+        check(kde_speckle_components_device(h_, &p));
+        return p;
+    }
+    const uint32_t* components_Host() const
+    {
+        const uint32_t* p = nullptr;
+        check(kde_speckle_components_host(h_, stream_, &p));
+        return p;
+    }
+    // 0; anything else is a defect of the library and the frame is not to be trusted
+    const uint32_t* capped_Host() const
+    {
+        const uint32_t* p = nullptr;
+        check(kde_speckle_capped_host(h_, stream_, &p));
+        return p;
+    }
+    uint32_t* capped_Device() const
+    {
+        uint32_t* p = nullptr;
+        check(kde_speckle_capped_device(h_, &p));
+        return p;
+    }
+
+private:
+    using DepthStage::filled_Device;        // this stage fills nothing: the names above say what the count is
+    using DepthStage::filled_Host;
+};
+
 }  // namespace kde
 
 #ifndef KDE_NO_GLOBAL_NAMES

@@ -974,6 +974,70 @@ int kde_holefill_passes_per_launch(kde_holefill* h, int* out);
 int kde_holefill_space_table(kde_holefill* h, float* table_host, int capacity);
 int kde_holefill_range_table(kde_holefill* h, float* table_host, int capacity);
 
+/* ==========================================================================================
+ * DepthSpeckleFilter: wrong depth taken away.  The registration's point mode lets background samples show through the cracks
+ * of an upscaled foreground, a time-of-flight sensor delivers flying pixels along every silhouette, a Kinect speckles inside
+ * its shadow bands; the stages behind treat such pixels as data (the hole filler fills the hole around a speckle from the
+ * speckle).  This stage labels the connected components of a frame under a depth-difference link and sets the components
+ * smaller than min_size to 0, as OpenCV's filterSpeckles does: the complement of DepthHoleFilling -- invalidate first, then
+ * fill.  For a batch on the device.  No reference counterpart, no colour guide.
+ *
+ * Frames: depth width x height (KDE_DEPTH_F32 or KDE_DEPTH_U16, uint16 widened by (float)u), the output (either format) and
+ * the optional labels (int32) of the same size.
+ *
+ * The rule.  Every operation is one IEEE binary32 operation in the order written, no fused multiply-add.
+ *   1. State.  z = (d > z_min && d < z_max) ? (float)d : 0 (NaN and +-inf become 0).
+ *   2. Link.  Two neighbouring pixels a, b are linked iff both have z > 0 and
+ *        fabsf(za - zb) <= max_diff + rel_diff * fminf(za, zb)
+ *      with the product and the sum rounded separately.  Neighbours are horizontal or vertical for connectivity 4, plus the
+ *      two diagonals for 8.
+ *   3. Component.  A component is a class of the transitive closure of the links.  Its label is the smallest raster index
+ *      y * width + x among its pixels, within its frame; its size is its pixel count.
+ *   4. Output.  z where the component's size is >= min_size, 0 elsewhere; for KDE_DEPTH_U16 depth_to_u16 of that, as
+ *      kde_points_to_depth rounds.  labels is the label of a kept pixel and -1 where the output is 0.  Per frame, counted before
+ *      the uint16 rounding: removed[f] = the number of pixels with z > 0 whose output is 0, components[f] = the number of kept
+ *      components, capped[f] = the number of threads that ran into the hard iteration cap of a loop: 0; anything else is a
+ *      defect of the library and the frame is not to be trusted.  min_size 1 removes nothing and is plain labelling.
+ * The result is a function of the input frame alone: labels are component minima and the counts integer sums, both order-free,
+ * so the bytes do not depend on n, a frame's position in the batch, pointer alignment, the tile shape or the order in which
+ * atomics land.
+ * ========================================================================================== */
+typedef struct kde_speckle_params { int min_size; float max_diff; float rel_diff; int connectivity; float z_min, z_max; } kde_speckle_params;
+typedef struct kde_speckle kde_speckle;
+/* min_size 64, max_diff 10 (millimetres), rel_diff 0.02, connectivity 4, z_min 0, z_max FLT_MAX */
+int kde_speckle_default_params(kde_speckle_params* p);
+/* frames of width x height, max_batch of them on the current device; p == NULL: the defaults.  KDE_ERR_INVALID: sizes below 1,
+ * a side above 2^24 or width * height above 2^30, min_size outside 1..2^24, max_diff or rel_diff not finite or < 0,
+ * connectivity neither 4 nor 8, z_min not finite or < 0, z_min >= z_max.  The object owns the union-find table and the sizes
+ * (two 4-byte words per pixel of max_batch frames), three counts per frame and per workgroup, and max_batch * width * height
+ * floats for calls with out_dev == NULL.  On a host without a device the object is created without buffers: every call
+ * validates as usual and the launch then returns KDE_ERR_HIP. */
+int kde_speckle_create(kde_speckle** out, int width, int height, int max_batch, const kde_speckle_params* p);
+int kde_speckle_destroy(kde_speckle* h);   /* NULL is a no-op */
+/* n <= max_batch frames: depth_dev is [n][height][width] of depth_format (KDE_DEPTH_F32 | KDE_DEPTH_U16), out_dev is
+ * [n][height][width] of out_format or NULL for the object-owned buffer, labels_dev is [n][height][width] int32 or NULL where
+ * it is not wanted.  Pointers need the alignment of their element only.  In place is allowed exactly when out_dev == depth_dev
+ * and out_format == depth_format (the last step reads a pixel and then writes it, every step before it only reads the input);
+ * any other overlap of the frames that are written -- out_dev's, or with out_dev == NULL the object-owned buffer's, which
+ * kde_speckle_depth_device hands out -- with those of depth_dev is KDE_ERR_INVALID, and so is labels_dev overlapping either.
+ * Five launches (three for a frame of one 32 x 16 tile): the tiles labelled in on-chip memory, the components united across
+ * the tile seams with atomic minima, the sizes summed at the roots, the output, the sums of the counts.  No workgroup waits
+ * for another and every loop is bounded; no memset node and nothing to reset (the words a call accumulates into are
+ * initialised by its own first kernel); no allocation, no host synchronisation: capturable from the first call. */
+int kde_speckle_filter_batch(kde_speckle* h, int n, const void* depth_dev, int depth_format, int out_format, void* out_dev,
+                             int32_t* labels_dev /* NULL: not wanted */, void* stream);
+/* the frames of the last kde_speckle_filter_batch: out_dev of that call or the object-owned buffer, in that call's out_format;
+ * valid until the next call or destroy.  KDE_ERR_INVALID before the first call (this and the seven getters below). */
+int kde_speckle_depth_device(kde_speckle* h, void** out);
+/* the same in pinned host memory after a blocking copy on `stream`: synchronises; out_dev of the last call must still be alive */
+int kde_speckle_depth_host(kde_speckle* h, void* stream, const void** out);
+int kde_speckle_removed_device(kde_speckle* h, uint32_t** out);   /* removed[n] of the last kde_speckle_filter_batch, on the device */
+int kde_speckle_removed_host(kde_speckle* h, void* stream, const uint32_t** out);   /* in pinned host memory: synchronises */
+int kde_speckle_components_device(kde_speckle* h, uint32_t** out);   /* components[n] of the last call, on the device */
+int kde_speckle_components_host(kde_speckle* h, void* stream, const uint32_t** out);   /* synchronises */
+int kde_speckle_capped_device(kde_speckle* h, uint32_t** out);   /* capped[n] of the last call, on the device: 0 in a correct library */
+int kde_speckle_capped_host(kde_speckle* h, void* stream, const uint32_t** out);   /* synchronises */
+
 #ifdef __cplusplus
 }
 #endif

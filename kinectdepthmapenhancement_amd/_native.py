@@ -140,6 +140,18 @@ class HolefillParams(C.Structure):
                 ("passes_per_launch", C.c_int)]
 
 
+class SpeckleHandle(C.c_void_p):
+    """kde_speckle*: a ctypes type of its own, like HolefillHandle, which keeps the kde_speckle_* entry points out of the frozen
+    record tools/abi_refusals.py enumerates; tests/test_speckle_abi.py checks their refusals."""
+
+
+class SpeckleParams(C.Structure):
+    """kde_speckle_params (defaults: 64, 10, 0.02, 4, 0, FLT_MAX -- components below 64 pixels go, a link holds within 10 mm
+    + 2 % of the nearer depth, 4-connected, every finite positive depth)."""
+    _fields_ = [("min_size", C.c_int), ("max_diff", C.c_float), ("rel_diff", C.c_float), ("connectivity", C.c_int),
+                ("z_min", C.c_float), ("z_max", C.c_float)]
+
+
 def build(force: bool = False) -> str:
     """Compile libkde_hip.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     if force:
@@ -362,6 +374,18 @@ SIGNATURES = {
     "kde_holefill_passes_per_launch": (_i, [HolefillHandle, C.POINTER(_i)]),
     "kde_holefill_space_table": (_i, [HolefillHandle, _vp, _i]),
     "kde_holefill_range_table": (_i, [HolefillHandle, _vp, _i]),
+    "kde_speckle_default_params": (_i, [C.POINTER(SpeckleParams)]),
+    "kde_speckle_create": (_i, [C.POINTER(SpeckleHandle), _i, _i, _i, C.POINTER(SpeckleParams)]),
+    "kde_speckle_destroy": (_i, [SpeckleHandle]),
+    "kde_speckle_filter_batch": (_i, [SpeckleHandle, _i, _vp, _i, _i, _vp, _vp, _vp]),
+    "kde_speckle_depth_device": (_i, [SpeckleHandle, _pp]),
+    "kde_speckle_depth_host": (_i, [SpeckleHandle, _vp, _pp]),
+    "kde_speckle_removed_device": (_i, [SpeckleHandle, _pp]),
+    "kde_speckle_removed_host": (_i, [SpeckleHandle, _vp, _pp]),
+    "kde_speckle_components_device": (_i, [SpeckleHandle, _pp]),
+    "kde_speckle_components_host": (_i, [SpeckleHandle, _vp, _pp]),
+    "kde_speckle_capped_device": (_i, [SpeckleHandle, _pp]),
+    "kde_speckle_capped_host": (_i, [SpeckleHandle, _vp, _pp]),
 }
 
 

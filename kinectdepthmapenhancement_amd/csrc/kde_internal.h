@@ -351,6 +351,30 @@ unsigned holefill_groups(int w, int h);                       // workgroups per 
 // ceil(iterations / fuse) launches of the fill kernel, then filled / remaining = the sums of the last one's counts
 int launch_holefill(const HolefillLaunch& a, hipStream_t s);
 
+// DepthSpeckleFilter (speckle_kernels.hip): connected components under a depth link, the small ones removed
+constexpr int kSpeckleMaxSize = 1 << 24;           // min_size, at the most
+constexpr int kSpeckleTileW = 32, kSpeckleTileH = 16;      // pixels of a workgroup's tile
+struct SpeckleLaunch {
+    int n;
+    int w, h;
+    int min_size, connectivity;                    // 1 .. kSpeckleMaxSize; 4 or 8
+    float max_diff, rel_diff, z_min, z_max;
+    const void* depth;                             // [n][h][w] float or uint16
+    int depth_format;
+    void* out;                                     // [n][h][w] float or uint16; may be depth itself in depth's format
+    int out_format;
+    int32_t* labels;                               // [n][h][w] or nullptr
+    int32_t* parent;                               // [n][h][w]: the union-find table, raster indices within a frame, -1 invalid
+    uint32_t* size;                                // [n][h][w]: pixels of a local component at its local root, of a component at its root
+    uint32_t* partial;                             // [n][speckle_groups(w, h)][3]: removed, kept roots, caps of each workgroup
+    uint32_t* removed;                             // [n]
+    uint32_t* components;                          // [n]
+    uint32_t* capped;                              // [n]
+};
+unsigned speckle_groups(int w, int h);                        // workgroups per frame
+// 5 kernels (3 for a frame of one tile): tile labelling, seam unions, resolve, apply, the sums of the counts
+int launch_speckle(const SpeckleLaunch& a, hipStream_t s);
+
 struct DaspGeom {
     int width, height, rows, cols, wx, wy;
 };

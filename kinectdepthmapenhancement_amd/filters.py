@@ -1270,6 +1270,65 @@ class DepthHoleFilling(_DepthStage):
         return self._count_device(lib().kde_holefill_remaining_device)
 
 
+class DepthSpeckleFilter(_DepthStage):
+    """Wrong depth taken away on the device (kde_speckle_*): the connected components of a frame under a depth-difference
+    link, those smaller than `min_size` set to 0 -- flying pixels, speckles, background showing through a registered
+    foreground.  It sits behind registration, undistortion and upsampling and in front of DepthHoleFilling: invalidate
+    first, then fill.  size is (width, height); params is a SpeckleParams (min_size, max_diff, rel_diff, connectivity,
+    z_min, z_max) or None for the defaults (64, 10 mm, 0.02, 4, every finite positive depth).  The rule is stated in
+    include/kde_hip.h; deterministic to the bit.  This stage fills nothing: its counts are removed(), components() and
+    capped()."""
+    _destroy, _prefix = "kde_speckle_destroy", "kde_speckle_"
+    _handle_type, _params_type = _native.SpeckleHandle, _native.SpeckleParams
+
+    def __init__(self, size, max_batch: int = 1, params: Optional["_native.SpeckleParams"] = None):
+        super().__init__(max_batch)
+        self.width, self.height = size
+        self._out_hw = (self.height, self.width)
+        check(lib().kde_speckle_create(C.byref(self._h), self.width, self.height, max_batch, None if params is None else C.byref(params)))
+
+    def filter(self, depth: torch.Tensor, out: Optional[torch.Tensor] = None, out_format=torch.float32,
+               labels: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """depth: [n,H,W] float32, or uint16 / int16 holding the sensor's uint16.  out: [n,H,W] float32 or uint16 / int16 (its
+        dtype is the output format), or None for the object-owned buffer in out_format (torch.float32, torch.uint16 or
+        torch.int16); `out` may be `depth` itself (in place) and must not overlap it otherwise.  labels: int32 [n,H,W] or
+        None: the smallest raster index of a kept pixel's component, -1 where the output is 0.  Returns the filtered frames.
+        Asynchronous on torch's current stream; no allocation, copy or synchronisation on the device."""
+        n, fmt = self._check_depth(depth, self.height, self.width)
+        ofmt = self._out_format(out, out_format, n)
+        if labels is not None:
+            _req(labels, torch.int32, (n, self.height, self.width), "labels")
+        check(lib().kde_speckle_filter_batch(self._h, n, depth.data_ptr(), fmt, ofmt, _ptr(out), _ptr(labels), _stream()))
+        return self._finished(n, ofmt, out)
+
+    def filled(self):
+        raise AttributeError("DepthSpeckleFilter fills nothing: removed(), components() and capped() are its counts")
+
+    filled_device = filled
+
+    def removed(self) -> np.ndarray:
+        """the number of pixels per frame that had a depth and lost it in the last filter(), uint32 [n]; synchronises"""
+        return self._count_host(lib().kde_speckle_removed_host)
+
+    def removed_device(self) -> torch.Tensor:
+        """removed on the device, as raw bytes [n, 4] (uint32), a view of the object-owned buffer"""
+        return self._count_device(lib().kde_speckle_removed_device)
+
+    def components(self) -> np.ndarray:
+        """the number of components per frame the last filter() kept, uint32 [n]; synchronises"""
+        return self._count_host(lib().kde_speckle_components_host)
+
+    def components_device(self) -> torch.Tensor:
+        return self._count_device(lib().kde_speckle_components_device)
+
+    def capped(self) -> np.ndarray:
+        """uint32 [n]: 0; anything else is a defect of the library and the frame is not to be trusted; synchronises"""
+        return self._count_host(lib().kde_speckle_capped_host)
+
+    def capped_device(self) -> torch.Tensor:
+        return self._count_device(lib().kde_speckle_capped_device)
+
+
 COMPARE_METHODS = ("input", "jbf", "mrf", "rgbf", "kde")
 
 
