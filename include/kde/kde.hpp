@@ -1498,6 +1498,67 @@ private:
     using DepthStage::filled_Host;
 };
 
+// extension (no reference counterpart; Buffer2D's sequence average folds n frames into one and has no notion of motion):
+// motion-aware smoothing of a depth sequence on the device (kde_temporal_*).  Each sample is blended into a per-pixel running
+// value while it stays on the same surface (DepthSpeckleFilter's link), starts the value again where it jumps, the value is
+// held over short dropouts and forgotten where the colour guide says the scene changed.  The frames of a call are consecutive
+// in time and the object carries the state from one call to the next; reset() starts a new sequence.  Beside
+// DepthSpeckleFilter and in front of DepthHoleFilling.  The rule is stated in kde_hip.h; deterministic to the bit, however the
+// sequence is cut into calls.  filter() and reset() are asynchronous on the object's stream and capturable (a replay advances
+// the stream by n frames); the *_Host members synchronise.  The count of the shared core is smoothed[f] here.
+class DepthTemporalFilter
+    : public detail::DepthStage<kde_temporal, kde_temporal_params, kde_temporal_default_params, kde_temporal_destroy, kde_temporal_depth_device,
+                                kde_temporal_depth_host, kde_temporal_smoothed_device, kde_temporal_smoothed_host> {
+public:
+    DepthTemporalFilter(int width, int height, int max_batch = 1) { check(kde_temporal_create(&h_, width, height, max_batch, nullptr)); }
+    DepthTemporalFilter(int width, int height, int max_batch, const kde_temporal_params& params)
+    {
+        check(kde_temporal_create(&h_, width, height, max_batch, &params));
+    }
+
+    // the next n frames of the sequence, back to back; bgr_device: n frames of guide or nullptr; the output format is the type
+    // of out_device (nullptr of that type: the object-owned buffer); out_device may be depth_device itself (in place) and must
+    // not overlap it otherwise, nor the guide
+    template <class Depth, class Out>
+    void filter(int n, const Depth* depth_device, const uint8_t* bgr_device, Out* out_device)
+    {
+        check(kde_temporal_filter_batch(h_, n, depth_device, format(depth_device), bgr_device, format(out_device), out_device, stream_));
+    }
+    // the state of every pixel becomes empty, as after construction
+    void reset() { check(kde_temporal_reset(h_, stream_)); }
+    // the object-owned state: value[height][width], hist[height][width] (kde_hip.h); copy it out to checkpoint a stream, copy
+    // into it between calls to restore one or to move it to another object
+    void state_Device(float*& value, uint32_t*& hist) const { check(kde_temporal_state_device(h_, &value, &hist)); }
+    // the pixels per frame of the last filter() whose sample was blended into the running value
+    uint32_t* smoothed_Device() const { return filled_Device(); }
+    const uint32_t* smoothed_Host() const { return filled_Host(); }
+    // ... whose valid sample left the surface of the running value
+    uint32_t* jumped_Device() const { return count(kde_temporal_jumped_device); }
+    const uint32_t* jumped_Host() const { return count(kde_temporal_jumped_host); }
+    // ... the holes that kept the running value
+    uint32_t* held_Device() const { return count(kde_temporal_held_device); }
+    const uint32_t* held_Host() const { return count(kde_temporal_held_host); }
+    // ... whose running value the guide's colour change forgot
+    uint32_t* changed_Device() const { return count(kde_temporal_changed_device); }
+    const uint32_t* changed_Host() const { return count(kde_temporal_changed_host); }
+
+private:
+    using DepthStage::filled_Device;        // this stage fills nothing: the names above say what the count is
+    using DepthStage::filled_Host;
+    uint32_t* count(int (*get)(kde_temporal*, uint32_t**)) const
+    {
+        uint32_t* p = nullptr;
+        check(get(h_, &p));
+        return p;
+    }
+    const uint32_t* count(int (*get)(kde_temporal*, void*, const uint32_t**)) const
+    {
+        const uint32_t* p = nullptr;
+        check(get(h_, stream_, &p));
+        return p;
+    }
+};
+
 }  // namespace kde
 
 #ifndef KDE_NO_GLOBAL_NAMES

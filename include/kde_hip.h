@@ -1038,6 +1038,99 @@ int kde_speckle_components_host(kde_speckle* h, void* stream, const uint32_t** o
 int kde_speckle_capped_device(kde_speckle* h, uint32_t** out);   /* capped[n] of the last call, on the device: 0 in a correct library */
 int kde_speckle_capped_host(kde_speckle* h, void* stream, const uint32_t** out);   /* synchronises */
 
+/* ==========================================================================================
+ * DepthTemporalFilter: motion-aware smoothing of a depth sequence.  Every stage above looks at one frame; a camera delivers a
+ * sequence, and frame-to-frame noise survives the spatial filters while holes blink open and shut.  This stage blends each
+ * sample into a per-pixel running value while the sample stays on the same surface, starts again where it jumps, holds the
+ * value over short dropouts and forgets it where the colour guide says the scene changed.  It sits beside DepthSpeckleFilter
+ * and in front of DepthHoleFilling.  No reference counterpart (kde_buffer2d_update_sequence folds n frames into ONE plain
+ * average and has no notion of motion).
+ *
+ * The frames of a call are consecutive in time, and the object carries state from one call to the next.
+ *
+ * Frames: depth width x height (KDE_DEPTH_F32 or KDE_DEPTH_U16, uint16 widened by (float)u), the optional guide
+ * width x height x 3 (b, g, r bytes) and the output (either format) of the same size.
+ *
+ * State per pixel, object-owned: value (float32, 0 means none) and hist (uint32): bits 0-7 hold the raw validity of the last
+ * eight frames, bit 0 the newest; bits 8-31 hold the guide colour b | g << 8 | r << 16 of the previous frame, or 0 when no
+ * guide was ever given.  kde_temporal_create and kde_temporal_reset set both words to 0.
+ *
+ * The rule.  Every operation is one IEEE binary32 operation in the order written, no fused multiply-add.  For frame t of the
+ * call, in order, for a pixel with raw sample d and, if a guide is given, colour (b, g, r):
+ *   1. Sample.  z = (d > z_min && d < z_max) ? (float)d : 0 (NaN and +-inf become 0).
+ *   2. Scene change, only with a guide and color_thresh < 765.  If |b - b'| + |g - g'| + |r - r'| > color_thresh against the
+ *      stored colour (b', g', r'): value = 0 and hist &= ~0xFF.  On the first frame after a reset the stored colour is (0, 0, 0)
+ *      and the state is already empty, so no flag is needed.
+ *   3. Valid sample (z > 0).  prev = value.  If prev > 0 && fabsf(z - prev) <= max_diff + rel_diff * fminf(z, prev), then
+ *      out = prev + alpha * (z - prev), with the difference, the product and the sum each rounded on its own; otherwise
+ *      out = z.  hist[7:0] = (hist[7:0] << 1 | 1) & 0xFF.
+ *   4. Hole (z == 0).  prev = value.  If prev > 0 && persist_min >= 1 && popcount(hist[7:0]) >= persist_min, then out = prev
+ *      (the history before this frame's shift); otherwise out = 0.  hist[7:0] = (hist[7:0] << 1) & 0xFF.  A value is therefore
+ *      held for at most eight frames after the last valid sample.
+ *   5. Store.  value = out (the float, never the uint16 rounding); the colour bits become this frame's colour, or are left
+ *      unchanged without a guide.  The output is out; for KDE_DEPTH_U16 depth_to_u16(out), as kde_points_to_depth rounds.
+ * Per frame, integer sums taken before the uint16 rounding: smoothed[f] = the linked branch of step 3; jumped[f] = z > 0 &&
+ * prev > 0 and not linked; held[f] = step 4 with out > 0; changed[f] = step 2 fired on a pixel whose value was > 0.
+ * The result is a function of the sequence since the last reset and nothing else: the bytes do not depend on how the sequence
+ * is cut into calls, on n, pointer alignment, the pixels a thread owns or the frames it loads ahead.
+ *
+ * Several sensors are served by several objects; because the rule is per pixel they can also share one object on frames of
+ * height S * H.  A sequence does not shard across GPUs: frame t needs the state frame t - 1 left.
+ * ========================================================================================== */
+typedef struct kde_temporal_params { float alpha; float max_diff; float rel_diff; int persist_min; int color_thresh; float z_min, z_max; } kde_temporal_params;
+typedef struct kde_temporal kde_temporal;
+/* alpha 0.4, max_diff 10 (millimetres), rel_diff 0.02 (DepthSpeckleFilter's link: the two stages agree on what one surface is),
+ * persist_min 3, color_thresh 48, z_min 0, z_max FLT_MAX */
+int kde_temporal_default_params(kde_temporal_params* p);
+/* frames of width x height, at most max_batch of them per call, on the current device; p == NULL: the defaults.
+ * KDE_ERR_INVALID: sizes below 1, width * height above 2^30, alpha outside (0, 1] (1: pass-through plus hold), max_diff or
+ * rel_diff not finite or < 0, persist_min outside 0..8 (0: never hold), color_thresh outside 0..765 (765: the guide is never
+ * consulted), z_min not finite or < 0, z_min >= z_max.  The object owns the state (two 4-byte words per pixel, zeroed here),
+ * four counts per frame and per wavefront, and max_batch * width * height floats for calls with out_dev == NULL.  On a host
+ * without a device the object is created without buffers: every call validates as usual and the launch then returns
+ * KDE_ERR_HIP. */
+int kde_temporal_create(kde_temporal** out, int width, int height, int max_batch, const kde_temporal_params* p);
+int kde_temporal_destroy(kde_temporal* h);   /* NULL is a no-op */
+/* The next n <= max_batch frames of the sequence: depth_dev is [n][height][width] of depth_format (KDE_DEPTH_F32 |
+ * KDE_DEPTH_U16), bgr_dev is [n][height][width][3] bytes or NULL (no guide: step 2 does not run and the stored colour stays),
+ * out_dev is [n][height][width] of out_format or NULL for the object-owned buffer.  Pointers need the alignment of their
+ * element only.  In place is allowed exactly when out_dev == depth_dev and out_format == depth_format (each thread reads its
+ * pixel of frame t before it writes it); any other overlap of the frames that are written -- out_dev's, or with out_dev == NULL
+ * the object-owned buffer's, which kde_temporal_depth_device hands out -- with those of depth_dev is KDE_ERR_INVALID, and so is
+ * their overlap with bgr_dev.  Two launches: the filter, in which a thread reads the state of its pixels once, walks the n
+ * frames in time order with the state in registers and writes it once, and the sums of the counts.  No allocation, no host
+ * synchronisation and no memset node: capturable from the first call.  Replaying a captured graph advances the stream by n
+ * frames: a replay filters what the captured pointers hold then as the NEXT n frames of the sequence. */
+int kde_temporal_filter_batch(kde_temporal* h, int n, const void* depth_dev, int depth_format, const uint8_t* bgr_dev /* NULL: no guide */,
+                              int out_format, void* out_dev /* NULL: object-owned */, void* stream);
+/* Both state words of every pixel become 0, as after create: the next frame starts a sequence.  A launch on `stream`, not a
+ * memset node; capturable.  The getters below answer "kde_temporal_filter_batch was not called" again until the next call. */
+int kde_temporal_reset(kde_temporal* h, void* stream);
+/* The object-owned state in the layout above: value[height][width] float32 and hist[height][width] uint32, on the device
+ * (both NULL for an object created without a device).  Reading it between calls checkpoints a stream; writing to it between
+ * calls is allowed and is the way to restore a checkpoint, or to move a stream to another object with two copies.  The caller
+ * orders its copies with the calls (the same stream, or an event). */
+int kde_temporal_state_device(kde_temporal* h, float** value, uint32_t** hist);
+/* A measurement knob, not a parameter: the pixels a thread owns (1, 2, 4, 8) and the frames whose loads it issues ahead of the
+ * arithmetic (1, 2, 4); 0, 0: the library's choice, a function of the frame size and n (kde_temporal_shape reports it).  The
+ * bytes of every result are the same for every shape.  KDE_ERR_INVALID for anything else. */
+int kde_temporal_set_shape(kde_temporal* h, int pixels_per_thread, int unroll);
+int kde_temporal_shape(kde_temporal* h, int n, int* pixels_per_thread, int* unroll);   /* what a call of n frames would run */
+/* the frames of the last kde_temporal_filter_batch: out_dev of that call or the object-owned buffer, in that call's out_format;
+ * valid until the next call or destroy.  KDE_ERR_INVALID before the first call and after kde_temporal_reset (this and the nine
+ * getters below). */
+int kde_temporal_depth_device(kde_temporal* h, void** out);
+/* the same in pinned host memory after a blocking copy on `stream`: synchronises; out_dev of the last call must still be alive */
+int kde_temporal_depth_host(kde_temporal* h, void* stream, const void** out);
+int kde_temporal_smoothed_device(kde_temporal* h, uint32_t** out);   /* smoothed[n] of the last kde_temporal_filter_batch, on the device */
+int kde_temporal_smoothed_host(kde_temporal* h, void* stream, const uint32_t** out);   /* in pinned host memory: synchronises */
+int kde_temporal_jumped_device(kde_temporal* h, uint32_t** out);
+int kde_temporal_jumped_host(kde_temporal* h, void* stream, const uint32_t** out);   /* synchronises */
+int kde_temporal_held_device(kde_temporal* h, uint32_t** out);
+int kde_temporal_held_host(kde_temporal* h, void* stream, const uint32_t** out);   /* synchronises */
+int kde_temporal_changed_device(kde_temporal* h, uint32_t** out);
+int kde_temporal_changed_host(kde_temporal* h, void* stream, const uint32_t** out);   /* synchronises */
+
 #ifdef __cplusplus
 }
 #endif

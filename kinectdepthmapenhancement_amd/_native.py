@@ -152,6 +152,19 @@ class SpeckleParams(C.Structure):
                 ("z_min", C.c_float), ("z_max", C.c_float)]
 
 
+class TemporalHandle(C.c_void_p):
+    """kde_temporal*: a ctypes type of its own, like SpeckleHandle, which keeps the kde_temporal_* entry points out of the
+    frozen record tools/abi_refusals.py enumerates; tests/test_temporal_abi.py checks their refusals."""
+
+
+class TemporalParams(C.Structure):
+    """kde_temporal_params (defaults: 0.4, 10, 0.02, 3, 48, 0, FLT_MAX -- 0.4 of a linked sample, a link holds within 10 mm
+    + 2 % of the nearer depth, a hole is held behind 3 valid frames of the last 8, a colour step above 48 forgets, every
+    finite positive depth)."""
+    _fields_ = [("alpha", C.c_float), ("max_diff", C.c_float), ("rel_diff", C.c_float), ("persist_min", C.c_int),
+                ("color_thresh", C.c_int), ("z_min", C.c_float), ("z_max", C.c_float)]
+
+
 def build(force: bool = False) -> str:
     """Compile libkde_hip.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     if force:
@@ -386,6 +399,24 @@ SIGNATURES = {
     "kde_speckle_components_host": (_i, [SpeckleHandle, _vp, _pp]),
     "kde_speckle_capped_device": (_i, [SpeckleHandle, _pp]),
     "kde_speckle_capped_host": (_i, [SpeckleHandle, _vp, _pp]),
+    "kde_temporal_default_params": (_i, [C.POINTER(TemporalParams)]),
+    "kde_temporal_create": (_i, [C.POINTER(TemporalHandle), _i, _i, _i, C.POINTER(TemporalParams)]),
+    "kde_temporal_destroy": (_i, [TemporalHandle]),
+    "kde_temporal_filter_batch": (_i, [TemporalHandle, _i, _vp, _i, _vp, _i, _vp, _vp]),
+    "kde_temporal_reset": (_i, [TemporalHandle, _vp]),
+    "kde_temporal_state_device": (_i, [TemporalHandle, _pp, _pp]),
+    "kde_temporal_set_shape": (_i, [TemporalHandle, _i, _i]),
+    "kde_temporal_shape": (_i, [TemporalHandle, _i, C.POINTER(_i), C.POINTER(_i)]),
+    "kde_temporal_depth_device": (_i, [TemporalHandle, _pp]),
+    "kde_temporal_depth_host": (_i, [TemporalHandle, _vp, _pp]),
+    "kde_temporal_smoothed_device": (_i, [TemporalHandle, _pp]),
+    "kde_temporal_smoothed_host": (_i, [TemporalHandle, _vp, _pp]),
+    "kde_temporal_jumped_device": (_i, [TemporalHandle, _pp]),
+    "kde_temporal_jumped_host": (_i, [TemporalHandle, _vp, _pp]),
+    "kde_temporal_held_device": (_i, [TemporalHandle, _pp]),
+    "kde_temporal_held_host": (_i, [TemporalHandle, _vp, _pp]),
+    "kde_temporal_changed_device": (_i, [TemporalHandle, _pp]),
+    "kde_temporal_changed_host": (_i, [TemporalHandle, _vp, _pp]),
 }
 
 

@@ -375,6 +375,32 @@ unsigned speckle_groups(int w, int h);                        // workgroups per 
 // 5 kernels (3 for a frame of one tile): tile labelling, seam unions, resolve, apply, the sums of the counts
 int launch_speckle(const SpeckleLaunch& a, hipStream_t s);
 
+// DepthTemporalFilter (temporal_kernels.hip): a per-pixel running value over consecutive frames, the state kept between calls
+struct TemporalLaunch {
+    int n;
+    int w, h;
+    int pixels, unroll;                            // the pixels a thread owns (1, 2, 4, 8), the frames it loads ahead (1, 2, 4)
+    float alpha, max_diff, rel_diff, z_min, z_max;
+    int persist_min, color_thresh;                 // 0 .. 8; 0 .. 765
+    const void* depth;                             // [n][h][w] float or uint16
+    int depth_format;
+    const uint8_t* bgr;                            // [n][h][w][3] or nullptr
+    void* out;                                     // [n][h][w] float or uint16; may be depth itself in depth's format
+    int out_format;
+    int nt_store;                                  // != 0: the output streams past the cache
+    float* value;                                  // [h][w]: the state
+    uint32_t* hist;                                // [h][w]
+    uint32_t* partial;                             // [n][temporal_waves(w * h, pixels)][2]: smoothed | jumped << 16, held | changed << 16
+    uint32_t* counts;                              // smoothed[max_batch], jumped[max_batch], held[max_batch], changed[max_batch]
+    int max_batch;
+};
+unsigned temporal_waves(size_t px, int pixels);               // wavefronts of the filter launch
+void temporal_shape(size_t px, int n, int* pixels, int* unroll);   // the library's choice
+// 2 kernels: the filter, the sums of the counts
+int launch_temporal(const TemporalLaunch& a, hipStream_t s);
+// 1 kernel: both state words of px pixels to 0
+int launch_temporal_reset(float* value, uint32_t* hist, size_t px, hipStream_t s);
+
 struct DaspGeom {
     int width, height, rows, cols, wx, wy;
 };

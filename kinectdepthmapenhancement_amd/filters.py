@@ -1329,6 +1329,99 @@ class DepthSpeckleFilter(_DepthStage):
         return self._count_device(lib().kde_speckle_capped_device)
 
 
+class DepthTemporalFilter(_DepthStage):
+    """Motion-aware smoothing of a depth sequence on the device (kde_temporal_*): each sample is blended into a per-pixel
+    running value while it stays on the same surface, starts the value again where it jumps, the value is held over short
+    dropouts and forgotten where the colour guide says the scene changed.  The frames of a call are consecutive in time and
+    the object carries the state from one call to the next; reset() starts a new sequence.  It sits beside
+    DepthSpeckleFilter and in front of DepthHoleFilling.  size is (width, height); params is a TemporalParams (alpha,
+    max_diff, rel_diff, persist_min, color_thresh, z_min, z_max) or None for the defaults.  The rule is stated in
+    include/kde_hip.h; deterministic to the bit, however the sequence is cut into calls.  This stage fills nothing: its
+    counts are smoothed(), jumped(), held() and changed()."""
+    _destroy, _prefix = "kde_temporal_destroy", "kde_temporal_"
+    _handle_type, _params_type = _native.TemporalHandle, _native.TemporalParams
+
+    def __init__(self, size, max_batch: int = 1, params: Optional["_native.TemporalParams"] = None):
+        super().__init__(max_batch)
+        self.width, self.height = size
+        self._out_hw = (self.height, self.width)
+        check(lib().kde_temporal_create(C.byref(self._h), self.width, self.height, max_batch, None if params is None else C.byref(params)))
+
+    def filter(self, depth: torch.Tensor, bgr: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+               out_format=torch.float32) -> torch.Tensor:
+        """depth: the next n frames of the sequence, [n,H,W] float32, or uint16 / int16 holding the sensor's uint16.  bgr:
+        uint8 [n,H,W,3] or None (no guide).  out: [n,H,W] float32 or uint16 / int16 (its dtype is the output format), or None
+        for the object-owned buffer in out_format; `out` may be `depth` itself (in place) and must not overlap it otherwise.
+        Returns the filtered frames.  Asynchronous on torch's current stream; no allocation, copy or synchronisation on the
+        device."""
+        n, fmt = self._check_depth(depth, self.height, self.width)
+        ofmt = self._out_format(out, out_format, n)
+        if bgr is not None:
+            if not isinstance(bgr, torch.Tensor) or bgr.dim() != 4 or bgr.shape[0] != n:
+                raise ValueError(f"bgr: expected [{n},{self.height},{self.width},3] uint8 (a frame of guide per frame of depth)")
+            _req(bgr, torch.uint8, (n, self.height, self.width, 3), "bgr")
+        check(lib().kde_temporal_filter_batch(self._h, n, depth.data_ptr(), fmt, _ptr(bgr), ofmt, _ptr(out), _stream()))
+        return self._finished(n, ofmt, out)
+
+    def reset(self) -> None:
+        """the state of every pixel becomes empty, as after construction: the next frame starts a sequence.  A launch on
+        torch's current stream; the counts and depth_device() ask for a filter() again."""
+        check(lib().kde_temporal_reset(self._h, _stream()))
+        self._n = 0
+
+    def state(self):
+        """(value float32 [H,W], hist int32 [H,W] holding the uint32 bits): views of the object-owned state.  Cloning them
+        between calls checkpoints a stream; copying into them restores one, or moves it to another object."""
+        v, k = C.c_void_p(), C.c_void_p()
+        check(lib().kde_temporal_state_device(self._h, C.byref(v), C.byref(k)))
+        return _view(v.value, self._out_hw, torch.float32, self), _view(k.value, self._out_hw, torch.int32, self)
+
+    def set_shape(self, pixels_per_thread: int = 0, unroll: int = 0) -> None:
+        """a measurement knob: the pixels a thread owns and the frames it loads ahead (0, 0: the library's choice); the bytes
+        of every result are the same"""
+        check(lib().kde_temporal_set_shape(self._h, pixels_per_thread, unroll))
+
+    def shape(self, n: int):
+        """(pixels per thread, frames loaded ahead) a call of n frames would run"""
+        p, u = C.c_int(), C.c_int()
+        check(lib().kde_temporal_shape(self._h, n, C.byref(p), C.byref(u)))
+        return p.value, u.value
+
+    def filled(self):
+        raise AttributeError("DepthTemporalFilter fills nothing: smoothed(), jumped(), held() and changed() are its counts")
+
+    filled_device = filled
+
+    def smoothed(self) -> np.ndarray:
+        """the pixels per frame of the last filter() whose sample was blended into the running value, uint32 [n]; synchronises"""
+        return self._count_host(lib().kde_temporal_smoothed_host)
+
+    def smoothed_device(self) -> torch.Tensor:
+        """smoothed on the device, as raw bytes [n, 4] (uint32), a view of the object-owned buffer"""
+        return self._count_device(lib().kde_temporal_smoothed_device)
+
+    def jumped(self) -> np.ndarray:
+        """the pixels per frame whose valid sample left the surface of the running value, uint32 [n]; synchronises"""
+        return self._count_host(lib().kde_temporal_jumped_host)
+
+    def jumped_device(self) -> torch.Tensor:
+        return self._count_device(lib().kde_temporal_jumped_device)
+
+    def held(self) -> np.ndarray:
+        """the hole pixels per frame that kept the running value, uint32 [n]; synchronises"""
+        return self._count_host(lib().kde_temporal_held_host)
+
+    def held_device(self) -> torch.Tensor:
+        return self._count_device(lib().kde_temporal_held_device)
+
+    def changed(self) -> np.ndarray:
+        """the pixels per frame whose running value the guide's colour change forgot, uint32 [n]; synchronises"""
+        return self._count_host(lib().kde_temporal_changed_host)
+
+    def changed_device(self) -> torch.Tensor:
+        return self._count_device(lib().kde_temporal_changed_device)
+
+
 COMPARE_METHODS = ("input", "jbf", "mrf", "rgbf", "kde")
 
 

@@ -99,3 +99,40 @@ def make_batch(first_seed: int, n: int, width: int = 640, height: int = 480):
     for i in range(n):
         bgr[i], depth[i] = make_frame(first_seed + i, width, height)
     return bgr, depth
+
+
+def make_sequence(seed: int, n: int, width: int = 640, height: int = 480, step=(3, 1), dropout: float = 0.02):
+    """n consecutive frames of one scene for the temporal stage: the static scene of make_frame(seed) with one foreground
+    rectangle (a fifth of the width, a quarter of the height, 1000 mm, one colour) that moves `step` pixels per frame.  Depth
+    noise (make_frame's model), +-6 levels of colour noise and dropouts (a fraction `dropout` of the pixels) are drawn anew for every frame from
+    rand_u32, so a pixel of the static region sees the same truth under different noise in every frame.
+
+    Returns (bgr uint8 [n,H,W,3], depth float32 [n,H,W], truth float32 [n,H,W] noise-free, rect int [n,4] as x0, y0, x1, y1)."""
+    H, W = height, width
+    bgr0, _, truth0 = make_frame(seed, W, H, clean=True)
+    rw, rh = max(W // 5, 1), max(H // 4, 1)
+    x_start, y_start = W // 8, H // 3
+    pix = np.arange(H * W, dtype=np.uint64).reshape(H, W)
+    bgr = np.empty((n, H, W, 3), np.uint8)
+    depth = np.empty((n, H, W), np.float32)
+    truth = np.empty((n, H, W), np.float32)
+    rect = np.empty((n, 4), np.int64)
+    for t in range(n):
+        x0 = min(max(x_start + t * step[0], 0), W - 1)
+        y0 = min(max(y_start + t * step[1], 0), H - 1)
+        x1, y1 = min(x0 + rw, W), min(y0 + rh, H)
+        rect[t] = (x0, y0, x1, y1)
+        at = pix + np.uint64(t) * np.uint64(H * W)
+        c = bgr0.astype(np.int64)
+        c[y0:y1, x0:x1] = (30, 200, 230)
+        for k in range(3):                                  # +-6 levels of colour noise, drawn anew for every frame
+            c[..., k] += (rand_u32(seed, 18 + k, at) % np.uint64(13)).astype(np.int64) - 6
+        bgr[t] = np.clip(c, 0, 255).astype(np.uint8)
+        z = truth0.copy()
+        z[y0:y1, x0:x1] = 1000.0
+        truth[t] = z
+        half = (0.45 * 2.85 * (z / 10.0) ** 2 / 10000.0).astype(np.float32)
+        noisy = (z + half * (rand_unit(seed, 16, at) * 2.0 - 1.0)).astype(np.float32)
+        noisy[(z == 0) | (rand_unit(seed, 17, at) < dropout)] = 0.0
+        depth[t] = noisy
+    return bgr, depth, truth, rect
