@@ -1559,6 +1559,71 @@ private:
     }
 };
 
+// extension (no reference counterpart: every class of the reference runs at the size of the frame it is given): depth frames
+// and their colour guides made `factor` times smaller each way on the device (kde_decimate_*).  An output pixel is the lower
+// median (KDE_DECIMATE_MEDIAN) or the guarded mean (KDE_DECIMATE_MEAN) of the valid samples of its factor x factor block, 0
+// where fewer than min_valid are valid; the guide is the block's mean colour rounded half up.  The step down of a
+// multi-resolution chain: decimate, enhance at the small size, GuidedDepthUpsampling back under the full-resolution guide.
+// The rule is stated in kde_hip.h; deterministic to the bit.  decimate() and decimateColor() are asynchronous on the object's
+// stream and capturable; the *_Host members synchronise.
+class DepthDecimation
+    : public detail::DepthStage<kde_decimate, kde_decimate_params, kde_decimate_default_params, kde_decimate_destroy, kde_decimate_depth_device,
+                                kde_decimate_depth_host, kde_decimate_filled_device, kde_decimate_filled_host> {
+public:
+    DepthDecimation(int src_width, int src_height, int max_batch = 1) { check(kde_decimate_create(&h_, src_width, src_height, max_batch, nullptr)); }
+    DepthDecimation(int src_width, int src_height, int max_batch, const kde_decimate_params& params)
+    {
+        check(kde_decimate_create(&h_, src_width, src_height, max_batch, &params));
+    }
+
+    // ceil(src / factor) each way
+    int outWidth() const
+    {
+        int w = 0, h = 0;
+        check(kde_decimate_out_size(h_, &w, &h));
+        return w;
+    }
+    int outHeight() const
+    {
+        int w = 0, h = 0;
+        check(kde_decimate_out_size(h_, &w, &h));
+        return h;
+    }
+    // n frames back to back; the output format is the type of out_device (nullptr of that type: the object-owned buffer),
+    // which must not overlap depth_device
+    template <class Depth, class Out>
+    void decimate(int n, const Depth* depth_device, Out* out_device)
+    {
+        check(kde_decimate_depth_batch(h_, n, depth_device, format(depth_device), format(out_device), out_device, stream_));
+    }
+    // the guides of n frames, [n][src_height][src_width][3] to [n][outHeight()][outWidth()][3]
+    void decimateColor(int n, const uint8_t* bgr_device, uint8_t* out_bgr_device)
+    {
+        check(kde_decimate_color_batch(h_, n, bgr_device, out_bgr_device, stream_));
+    }
+    // the camera matrix of the small image: fx / k, fy / k, (cx + 0.5) / k - 0.5, (cy + 0.5) / k - 0.5; needs no device
+    template <class MatLike>
+    void intrinsics(const MatLike& intrinsic, double (&small_intrinsic)[9]) const
+    {
+        double k[9];
+        intrinsic_to_array(intrinsic, k);
+        check(kde_decimate_intrinsics(h_, k, small_intrinsic));
+    }
+    // the output pixels per frame of the last decimate() whose block spans more than max_gap (0 without a guard)
+    uint32_t* mixed_Device() const
+    {
+        uint32_t* p = nullptr;
+        check(kde_decimate_mixed_device(h_, &p));
+        return p;
+    }
+    const uint32_t* mixed_Host() const
+    {
+        const uint32_t* p = nullptr;
+        check(kde_decimate_mixed_host(h_, stream_, &p));
+        return p;
+    }
+};
+
 }  // namespace kde
 
 #ifndef KDE_NO_GLOBAL_NAMES

@@ -1131,6 +1131,82 @@ int kde_temporal_held_host(kde_temporal* h, void* stream, const uint32_t** out);
 int kde_temporal_changed_device(kde_temporal* h, uint32_t** out);
 int kde_temporal_changed_host(kde_temporal* h, void* stream, const uint32_t** out);   /* synchronises */
 
+/* ==========================================================================================
+ * DepthDecimation: depth frames, and their colour guides, made `factor` times smaller each way.  Every stage above, and every
+ * class of the reference, runs at the size of the frame it is given; this is the step down of a multi-resolution chain --
+ * decimate, enhance at the small size, GuidedDepthUpsampling back under the full-resolution guide -- and the cheapest
+ * denoiser there is.  An average pool mixes the sensor's 0 into valid depths and invents depths between two surfaces; strided
+ * indexing throws k^2 - 1 of k^2 samples away.  This stage is hole-aware and edge-aware.  No reference counterpart.
+ *
+ * Frames: depth src_w x src_h (KDE_DEPTH_F32 or KDE_DEPTH_U16, uint16 widened by (float)u); k = factor, an integer in 2..8; the
+ * output out_w = ceil(src_w / k) by out_h = ceil(src_h / k), in either format.  Output pixel (i, j) stands for the block of
+ * source pixels qy = j * k .. min(j * k + k, src_h) - 1 (outer loop), qx = i * k .. min(i * k + k, src_w) - 1 (inner loop):
+ * this loop order is the tap order.  Blocks on the right and bottom edge may be partial: they use only the samples that exist,
+ * and nothing is scaled for them.
+ *
+ * The rule.  Every operation is one IEEE binary32 operation in the order written, the division correctly rounded; nothing
+ * transcendental is evaluated.  Per output pixel:
+ *   1. A sample is valid iff z > z_min && z < z_max (NaN and +-inf fail).
+ *   2. m = the number of valid samples of the block.
+ *   3. If m < min_valid the pixel is 0 (the sensor's "invalid").  A partial block with fewer existing samples than min_valid is
+ *      therefore a hole.
+ *   4. zmed = the lower median of the valid samples: sorted ascending to v[0 .. m - 1], v[(m - 1) / 2].  It is always one of the
+ *      samples.
+ *   5. mode KDE_DECIMATE_MEDIAN: the pixel is zmed.  It never lies between two surfaces; uint16 in to uint16 out is exact.
+ *   6. mode KDE_DECIMATE_MEAN: num = 0, cnt = 0; for each valid sample in tap order with max_gap == 0 || fabsf(z - zmed) <=
+ *      max_gap: num = num + z, cnt = cnt + 1.  The pixel is num / (float)cnt; cnt >= 1 because zmed passes its own test.
+ *   7. The output is the float itself (KDE_DEPTH_F32) or depth_to_u16 of it as kde_points_to_depth rounds (KDE_DEPTH_U16).
+ *   8. filled[f] = the number of non-hole output pixels of frame f, counted before the uint16 rounding.
+ *   9. mixed[f] = the number of output pixels with m >= 1 whose largest valid sample minus smallest valid sample exceeds
+ *      max_gap: the blocks that straddle a depth edge.  It is 0 for every frame when max_gap == 0.
+ * The guide (kde_decimate_color_batch): per channel, s = the integer sum over the block's existing pixels and c their count;
+ * the output is (2 * s + c) / (2 * c) in integer division, the area mean rounded half up.  It is exact; it does not claim to
+ * equal OpenCV's INTER_AREA, which rounds half to even.
+ * The camera (kde_decimate_intrinsics): fx' = fx / k, fy' = fy / k, cx' = (cx + 0.5) / k - 0.5, cy' likewise, in doubles on the
+ * host: the pixel-centre rule, under which the centre of block (i, j) is pixel (i, j).  One limit: GuidedDepthUpsampling back to
+ * src_w x src_h assumes both images cover the same view, which holds exactly only when both sides are multiples of k.
+ * Every output pixel is a function of its own block and the counts are integer sums: the result is deterministic to the bit and
+ * does not depend on n, a frame's position in the batch or pointer alignment.
+ * ========================================================================================== */
+enum { KDE_DECIMATE_MEDIAN = 0, KDE_DECIMATE_MEAN = 1 };
+typedef struct kde_decimate_params { int factor; int mode; int min_valid; float max_gap; float z_min, z_max; } kde_decimate_params;
+typedef struct kde_decimate kde_decimate;
+/* factor 2, KDE_DECIMATE_MEDIAN, min_valid 1, max_gap 0 (no guard), z_min 0, z_max FLT_MAX */
+int kde_decimate_default_params(kde_decimate_params* p);
+/* source frames of src_w x src_h, at most max_batch of them per call, on the current device; p == NULL: the defaults.
+ * KDE_ERR_INVALID: sizes below 1 or a side above 2^24, factor outside 2..8, mode neither 0 nor 1, min_valid outside
+ * 1..factor^2, max_gap not finite or < 0, z_min not finite or < 0, z_min >= z_max.  The object owns filled[max_batch],
+ * mixed[max_batch], a count pair per workgroup and max_batch * out_w * out_h floats for calls with out_dev == NULL.  On a host
+ * without a device the object is created without buffers: every call validates as usual and the launch then returns
+ * KDE_ERR_HIP. */
+int kde_decimate_create(kde_decimate** out, int src_w, int src_h, int max_batch, const kde_decimate_params* p);
+int kde_decimate_destroy(kde_decimate* h);   /* NULL is a no-op */
+int kde_decimate_out_size(kde_decimate* h, int* out_w, int* out_h);   /* ceil(src_w / factor), ceil(src_h / factor); needs no device */
+/* n <= max_batch frames: depth_dev is [n][src_h][src_w] of depth_format (KDE_DEPTH_F32 | KDE_DEPTH_U16), out_dev is
+ * [n][out_h][out_w] of out_format or NULL for the object-owned buffer.  Pointers need the alignment of their element only:
+ * whatever the alignment, a source row is read as the aligned 16-byte pieces inside it and as elements at its two ends, with
+ * the same result.  In place is refused: the frames that are written -- out_dev's, or with out_dev == NULL the object-owned
+ * buffer's, which kde_decimate_depth_device hands out -- must not overlap those of depth_dev (KDE_ERR_INVALID).  Two launches:
+ * the decimation, whose workgroups each write their count pair, and the sum of those into filled[f] and mixed[f] -- no atomic,
+ * no memset node and nothing to reset; no allocation, no host synchronisation: capturable from the first call. */
+int kde_decimate_depth_batch(kde_decimate* h, int n, const void* depth_dev, int depth_format, int out_format, void* out_dev /* NULL: object-owned */,
+                             void* stream);
+/* the guides of n <= max_batch frames: bgr_dev is [n][src_h][src_w][3] bytes, out_bgr_dev [n][out_h][out_w][3]; any alignment;
+ * the two must not overlap (KDE_ERR_INVALID).  One launch; it leaves the results of the last kde_decimate_depth_batch alone. */
+int kde_decimate_color_batch(kde_decimate* h, int n, const uint8_t* bgr_dev, uint8_t* out_bgr_dev, void* stream);
+/* K_out[9] = the row-major 3 x 3 camera matrix of the small image for K_in[9] of the source image (K_out may be K_in): the
+ * rule above, the skew entries divided by k, the last row copied.  Doubles, on the host only: works without a device. */
+int kde_decimate_intrinsics(kde_decimate* h, const double* K_in, double* K_out);
+/* the frames of the last kde_decimate_depth_batch: out_dev of that call or the object-owned buffer, in that call's out_format;
+ * valid until the next call or destroy.  KDE_ERR_INVALID before the first call (this and the five getters below). */
+int kde_decimate_depth_device(kde_decimate* h, void** out);
+/* the same in pinned host memory after a blocking copy on `stream`: synchronises; out_dev of the last call must still be alive */
+int kde_decimate_depth_host(kde_decimate* h, void* stream, const void** out);
+int kde_decimate_filled_device(kde_decimate* h, uint32_t** out);   /* filled[n] of the last kde_decimate_depth_batch, on the device */
+int kde_decimate_filled_host(kde_decimate* h, void* stream, const uint32_t** out);   /* in pinned host memory: synchronises */
+int kde_decimate_mixed_device(kde_decimate* h, uint32_t** out);
+int kde_decimate_mixed_host(kde_decimate* h, void* stream, const uint32_t** out);   /* synchronises */
+
 #ifdef __cplusplus
 }
 #endif

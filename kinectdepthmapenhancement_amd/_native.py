@@ -165,6 +165,21 @@ class TemporalParams(C.Structure):
                 ("color_thresh", C.c_int), ("z_min", C.c_float), ("z_max", C.c_float)]
 
 
+class DecimateHandle(C.c_void_p):
+    """kde_decimate*: a ctypes type of its own, like TemporalHandle, which keeps the kde_decimate_* entry points out of the
+    frozen record tools/abi_refusals.py enumerates; tests/test_decimate_abi.py checks their refusals."""
+
+
+class DecimateParams(C.Structure):
+    """kde_decimate_params (defaults: 2, KDE_DECIMATE_MEDIAN, 1, 0, 0, FLT_MAX -- half the size each way, the lower median of
+    at least one valid sample, no guard, every finite positive depth)."""
+    _fields_ = [("factor", C.c_int), ("mode", C.c_int), ("min_valid", C.c_int), ("max_gap", C.c_float), ("z_min", C.c_float),
+                ("z_max", C.c_float)]
+
+
+KDE_DECIMATE_MEDIAN, KDE_DECIMATE_MEAN = 0, 1
+
+
 def build(force: bool = False) -> str:
     """Compile libkde_hip.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     if force:
@@ -417,6 +432,19 @@ SIGNATURES = {
     "kde_temporal_held_host": (_i, [TemporalHandle, _vp, _pp]),
     "kde_temporal_changed_device": (_i, [TemporalHandle, _pp]),
     "kde_temporal_changed_host": (_i, [TemporalHandle, _vp, _pp]),
+    "kde_decimate_default_params": (_i, [C.POINTER(DecimateParams)]),
+    "kde_decimate_create": (_i, [C.POINTER(DecimateHandle), _i, _i, _i, C.POINTER(DecimateParams)]),
+    "kde_decimate_destroy": (_i, [DecimateHandle]),
+    "kde_decimate_out_size": (_i, [DecimateHandle, C.POINTER(_i), C.POINTER(_i)]),
+    "kde_decimate_depth_batch": (_i, [DecimateHandle, _i, _vp, _i, _i, _vp, _vp]),
+    "kde_decimate_color_batch": (_i, [DecimateHandle, _i, _vp, _vp, _vp]),
+    "kde_decimate_intrinsics": (_i, [DecimateHandle, _vp, _vp]),
+    "kde_decimate_depth_device": (_i, [DecimateHandle, _pp]),
+    "kde_decimate_depth_host": (_i, [DecimateHandle, _vp, _pp]),
+    "kde_decimate_filled_device": (_i, [DecimateHandle, _pp]),
+    "kde_decimate_filled_host": (_i, [DecimateHandle, _vp, _pp]),
+    "kde_decimate_mixed_device": (_i, [DecimateHandle, _pp]),
+    "kde_decimate_mixed_host": (_i, [DecimateHandle, _vp, _pp]),
 }
 
 

@@ -108,13 +108,15 @@ struct DepthStage {
     }
     // For a stage whose workgroups read their neighbours' input while those write (DepthHoleFilling; the gathers and the scatter
     // of the other three allow what they allow).  The buffer that is written is the caller's or the object's own, which a caller
-    // holds after *_depth_device (a device-less object has none).  px: the pixels of the whole call.
-    int check_not_in_place(const char* who, const void* depth_dev, int depth_format, void* out_dev, int out_format, size_t px) const
+    // holds after *_depth_device (a device-less object has none).  px: the pixels of the whole call; out_px: those it writes,
+    // where they are fewer (DepthDecimation); 0, the default, means the same as px.
+    int check_not_in_place(const char* who, const void* depth_dev, int depth_format, void* out_dev, int out_format, size_t px,
+                           size_t out_px = 0) const
     {
         const void* w = written(out_dev);
         if (!w) return KDE_OK;
         const uintptr_t d0 = reinterpret_cast<uintptr_t>(depth_dev), d1 = d0 + px * depth_element(depth_format);
-        const uintptr_t o0 = reinterpret_cast<uintptr_t>(w), o1 = o0 + px * depth_element(out_format);
+        const uintptr_t o0 = reinterpret_cast<uintptr_t>(w), o1 = o0 + (out_px ? out_px : px) * depth_element(out_format);
         KDE_REQUIRE(o1 <= d0 || d1 <= o0, "%s: %s overlaps depth_dev (in place is not supported)", who,
                     out_dev ? "out_dev" : "the object-owned output buffer, which out_dev == NULL selects,");
         return KDE_OK;

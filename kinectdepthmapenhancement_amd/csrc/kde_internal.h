@@ -401,6 +401,27 @@ int launch_temporal(const TemporalLaunch& a, hipStream_t s);
 // 1 kernel: both state words of px pixels to 0
 int launch_temporal_reset(float* value, uint32_t* hist, size_t px, hipStream_t s);
 
+// DepthDecimation (decimate_kernels.hip): frames made `factor` times smaller each way, a pixel from the valid samples of its block
+struct DecimateLaunch {
+    int n;
+    int sw, sh, ow, oh;                            // source and output frame: ow = ceil(sw / factor), oh likewise
+    int factor;                                    // 2 .. 8
+    int mode, min_valid;                           // KDE_DECIMATE_MEDIAN | KDE_DECIMATE_MEAN; 1 .. factor^2
+    float max_gap, z_min, z_max;                   // max_gap 0: no guard
+    const void* depth;                             // [n][sh][sw] float or uint16
+    int depth_format;
+    void* out;                                     // [n][oh][ow] float or uint16
+    int out_format;
+    uint32_t* partial;                             // [n][decimate_groups(ow, oh, factor)][2]: filled, mixed of each workgroup
+    uint32_t* filled;                              // [n]
+    uint32_t* mixed;                               // [n]
+    const uint8_t* bgr;                            // the colour call: [n][sh][sw][3]
+    uint8_t* out_bgr;                              //                  [n][oh][ow][3]
+};
+unsigned decimate_groups(int ow, int oh, int factor);         // workgroups per frame
+int launch_decimate(const DecimateLaunch& a, hipStream_t s);  // 2 kernels: the decimation, the sums of its counts
+int launch_decimate_color(const DecimateLaunch& a, hipStream_t s);   // 1 kernel
+
 struct DaspGeom {
     int width, height, rows, cols, wx, wy;
 };

@@ -1422,6 +1422,76 @@ class DepthTemporalFilter(_DepthStage):
         return self._count_device(lib().kde_temporal_changed_device)
 
 
+class DepthDecimation(_DepthStage):
+    """Depth frames and their colour guides made `factor` times smaller each way on the device (kde_decimate_*): an output pixel
+    is the lower median (KDE_DECIMATE_MEDIAN) or the guarded mean (KDE_DECIMATE_MEAN) of the valid samples of its factor x
+    factor block, 0 where fewer than min_valid are valid; the guide is the block's mean colour rounded half up.  The step down
+    of a multi-resolution chain: decimate, enhance at the small size, GuidedDepthUpsampling back under the full-resolution
+    guide.  src_size is (width, height); params is a DecimateParams (factor, mode, min_valid, max_gap, z_min, z_max) or None for
+    the defaults (2, median, 1, no guard, every finite positive depth).  The rule is stated in include/kde_hip.h;
+    deterministic to the bit.  Its counts are filled() and mixed()."""
+    _destroy, _prefix = "kde_decimate_destroy", "kde_decimate_"
+    _handle_type, _params_type = _native.DecimateHandle, _native.DecimateParams
+
+    def __init__(self, src_size, max_batch: int = 1, params: Optional["_native.DecimateParams"] = None):
+        super().__init__(max_batch)
+        self.src_width, self.src_height = src_size
+        check(lib().kde_decimate_create(C.byref(self._h), self.src_width, self.src_height, max_batch, None if params is None else C.byref(params)))
+        w, h = C.c_int(), C.c_int()
+        check(lib().kde_decimate_out_size(self._h, C.byref(w), C.byref(h)))
+        self.out_width, self.out_height = w.value, h.value
+        self._out_hw = (self.out_height, self.out_width)
+
+    @property
+    def out_size(self):
+        """(width, height) of an output frame: ceil(src / factor) each way"""
+        return self.out_width, self.out_height
+
+    def decimate(self, depth: torch.Tensor, out: Optional[torch.Tensor] = None, out_format=None) -> torch.Tensor:
+        """depth: [n,Hs,Ws] float32, or uint16 / int16 holding the sensor's uint16.  out: [n,Ho,Wo] float32 or uint16 / int16 (its
+        dtype is the output format), or None for the object-owned buffer in out_format (torch.float32, torch.uint16 or
+        torch.int16; None: the format of depth); what is written must not overlap depth.  Returns the decimated frames (0
+        where a block had fewer than min_valid valid samples).  Asynchronous on torch's current stream; no allocation, copy or
+        synchronisation on the device."""
+        n, fmt = self._check_depth(depth, self.src_height, self.src_width)
+        if out is None and out_format is None:
+            out_format = torch.float32 if fmt == _native.KDE_DEPTH_F32 else torch.int16
+        ofmt = self._out_format(out, out_format, n)
+        check(lib().kde_decimate_depth_batch(self._h, n, depth.data_ptr(), fmt, ofmt, _ptr(out), _stream()))
+        return self._finished(n, ofmt, out)
+
+    def decimate_color(self, bgr: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """bgr: uint8 [n,Hs,Ws,3].  Returns uint8 [n,Ho,Wo,3], the mean colour of each block rounded half up.  Asynchronous on
+        torch's current stream; it leaves the results of the last decimate() alone."""
+        if not isinstance(bgr, torch.Tensor) or bgr.dim() != 4:
+            raise ValueError(f"bgr: expected [n,{self.src_height},{self.src_width},3] uint8")
+        n = bgr.shape[0]
+        _req(bgr, torch.uint8, (n, self.src_height, self.src_width, 3), "bgr")
+        if out is None:
+            out = torch.empty((n, self.out_height, self.out_width, 3), dtype=torch.uint8, device=bgr.device)
+        else:
+            _req(out, torch.uint8, (n, self.out_height, self.out_width, 3), "out")
+        check(lib().kde_decimate_color_batch(self._h, n, bgr.data_ptr(), out.data_ptr(), _stream()))
+        return out
+
+    def intrinsics(self, K) -> np.ndarray:
+        """the 3 x 3 camera matrix of the small image for K of the source image, float64: fx / k, fy / k, (cx + 0.5) / k - 0.5,
+        (cy + 0.5) / k - 0.5; needs no device"""
+        k = _K9(K)
+        r = np.empty(9, np.float64)
+        check(lib().kde_decimate_intrinsics(self._h, k.ctypes.data, r.ctypes.data))
+        return r.reshape(3, 3)
+
+    def mixed(self) -> np.ndarray:
+        """the output pixels per frame of the last decimate() whose block spans more than max_gap, uint32 [n] (0 without a
+        guard); synchronises torch's current stream"""
+        return self._count_host(lib().kde_decimate_mixed_host)
+
+    def mixed_device(self) -> torch.Tensor:
+        """mixed on the device, as raw bytes [n, 4] (uint32), a view of the object-owned buffer"""
+        return self._count_device(lib().kde_decimate_mixed_device)
+
+
 COMPARE_METHODS = ("input", "jbf", "mrf", "rgbf", "kde")
 
 
