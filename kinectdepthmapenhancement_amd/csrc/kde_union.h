@@ -13,6 +13,14 @@
 // returns is the cell's true parent at that instant, and the link is carried on from there (old ~ hi was already true, so
 // hi ~ lo is established by old ~ lo).  A stale load therefore costs an iteration and never a link; the roots at the end are
 // the component minima.
+//
+// An amin() that REPLACES a parent old by a smaller v takes the link cell -> old out of the forest, so old ~ v has to hold
+// without it.  The union carries exactly that on (above).  The walk shortens paths only where it holds already: it aims x at
+// a value g that x's parent p has held (path halving).  p ~ g holds among the cells below x -- p held g --, and whatever x
+// holds by then replaced p under this same rule, so it is joined to p, and through p to g, among the cells below x as well.
+// (The first version aimed every cell it met at the root of its walk and went on along the parents those amin()s RETURNED:
+// cells that were never on the walk.  Where such a cell's parent had fallen below that root it stopped, and the link it had
+// just replaced was lost -- the randomised sweep found it, tests/speckle_cases.py `lost_link` keeps it.)
 #pragma once
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
@@ -41,13 +49,21 @@ KDE_UNION_FN int uf_find(Ops& m, int x, bool& capped)
     return x;
 }
 
-// the same, and every cell of the walk is then aimed at the root it found: amin() with a smaller index of the same component
+// the same, and every cell of the walk is aimed at a value its parent has held (path halving): amin() with a smaller index
+// that is joined to the cell's parents without the link the amin() may replace
 template <class Ops>
-KDE_UNION_FN int uf_find_compress(Ops& m, int x, bool& capped)
+KDE_UNION_FN int uf_find_halve(Ops& m, int x, bool& capped)
 {
-    const int root = uf_find(m, x, capped);
-    for (int i = 0; i < kUnionCap && x > root; i++) x = m.amin(x, root);    // x: the parent the cell had, smaller than the cell
-    return root;
+    for (int i = 0; i < kUnionCap; i++) {
+        const int p = m.load(x);
+        if (p >= x) return x;                   // a root holds itself
+        const int g = m.load(p);
+        if (g >= p) return p;
+        m.amin(x, g);
+        x = p;
+    }
+    capped = true;
+    return x;
 }
 
 // a ~ b
@@ -55,8 +71,8 @@ template <class Ops>
 KDE_UNION_FN void uf_union(Ops& m, int a, int b, bool& capped)
 {
     for (int i = 0; i < kUnionCap; i++) {
-        a = uf_find_compress(m, a, capped);
-        b = uf_find_compress(m, b, capped);
+        a = uf_find_halve(m, a, capped);
+        b = uf_find_halve(m, b, capped);
         if (capped || a == b) return;
         const int hi = a > b ? a : b, lo = a > b ? b : a;
         const int old = m.amin(hi, lo);

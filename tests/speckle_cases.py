@@ -11,6 +11,7 @@ binary32 and never fuses a multiply with an add):
              the output is 0; removed = the pixels with z > 0 and output 0, components = the kept components, both before any
              uint16 rounding
 """
+import os
 from collections import namedtuple
 
 import numpy as np
@@ -146,6 +147,11 @@ CASES = {c.name: c for c in (
     Case("noise", (100, 50), 3, {}, "white noise: nearly every pixel its own root, few merges: the most atomics per pixel"),
     Case("frame", (96, 64), 64, dict(z_min=Z_RANGE[0], z_max=Z_RANGE[1]), "the generator's frame with flying pixels along its depth edges, "
          "speckles in its holes and a tenth of the float depth NaN / +-inf / out of the z range"),
+    Case("lost_link", (128, 64), 8, dict(max_diff=0.0, rel_diff=0.004, z_min=Z_RANGE[0]), "4 x 4 copies of a tile of the randomised sweep "
+         "(tests/stage_sweep.py, speckle, seed 1, index 234, frame 0, tile (0, 3)): 65 local components and 495 links, among them chains "
+         "that other threads hook and compress while a thread walks them.  The first uf_find_compress aimed the cells it met at the "
+         "root of its walk and followed their CURRENT parents; where such a parent had fallen below that root it stopped, and a link "
+         "it had just replaced was lost: about one run in fifty split 7 pixels from their component.  Run repeatedly"),
 )}
 IDS = list(CASES)
 HUGE = 1 << 24
@@ -256,6 +262,10 @@ def depth_frames(name, integer=False):
             z = rng.uniform(500.0, 5000.0, (h, w)).astype(np.float32)
         elif name == "frame":
             z = injected_frame(f, w, h)[0]
+        elif name == "lost_link":
+            tile = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "speckle_lost_link_tile.npy")).astype(np.float32)
+            z = np.tile(tile, (4, 4))
+            z = np.where(z > 0, z + F(7.0 * f), F(0)).astype(np.float32)      # whole millimetres: the same frames as uint16
         if integer:
             with np.errstate(invalid="ignore"):
                 bad = ~np.isfinite(z) | (z < 0)

@@ -181,6 +181,42 @@ def test_batch_equals_single_calls_on_a_side_stream(T, method):
     g.close()
 
 
+def test_batch_across_more_than_one_chunk(T, R):
+    """launch_normals runs N3-N5 in chunks of normals_chunk_frames() frames and re-uses cnt and sums from chunk to chunk; 56
+    frames of 320 x 240 are 54 + 2: a second trip of the loop from a.pts + off, a.fs + off, a.out + off, and a last chunk with
+    nf = 2 < chunk_frames, whose plane stride k * nf * npx the row scan, the column scan and the CM kernel must agree on.
+    Every frame differs, so a chunk that read another chunk's sums shows; the last frame takes the uncapped distance transform."""
+    from kinectdepthmapenhancement_amd import filters
+    W, H, n = 320, 240, 56
+    chunk = min(max((1 << 22) // (W * H), 1), n)          # normals_chunk_frames, normal_kernels.hip:439-446
+    assert chunk == 54 and n > chunk and n % chunk == 2
+    pts = np.stack([ragged_points(500 + k, W, H) for k in range(n)])
+    pts[n - 1] = far_points(W, H)
+    dp = T.from_numpy(pts).cuda()
+    g = filters.NormalMapGenerator(W, H, max_batch=n)
+    for method in (g.CM, g.BILATERAL):
+        g.setNormalEstimationMethods(method)
+        singles, sfs = T.empty_like(dp), T.empty((n, H, W), dtype=T.float32, device="cuda")
+        for k in range(n):
+            g.generateNormalMap(dp[k])
+            singles[k].copy_(g.getNormalMap())
+            if method == g.CM:
+                sfs[k].copy_(g.getSmoothingMap())
+        out = T.zeros_like(dp)
+        g.generateNormalMapBatch(n, dp, out)
+        got, single = out.cpu().numpy(), singles.cpu().numpy()
+        diff = (bits(got) != bits(single)).reshape(n, -1).any(1)
+        assert not diff.any(), (method, "frames that differ from their single call", np.flatnonzero(diff).tolist())
+        if method == g.CM:
+            fs = g.getSmoothingMap().cpu().numpy()
+            fdiff = (bits(fs) != bits(sfs.cpu().numpy())).reshape(n, -1).any(1)
+            assert not fdiff.any(), ("smoothing maps that differ from their single call", np.flatnonzero(fdiff).tolist())
+            assert fs[n - 1].max() > 47.0                # the far frame's uncapped distance transform, in the last chunk
+            for k in (0, chunk, n - 1):                  # the first frame of each chunk and the last frame
+                check_cm(R, got[k], fs[k], pts[k], W * H // 100, f"frame {k} of {n}")
+    g.close()
+
+
 def test_graph_capture_replays_the_same_bytes(T):
     from kinectdepthmapenhancement_amd import filters
     W, H, n = 200, 150, 3
