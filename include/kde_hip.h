@@ -388,7 +388,9 @@ int kde_nasp_set_parameters(kde_nasp* h, int rows, int cols, const double* K9);
  * The weights of the weighted-average pass are host-built tables keyed by (color_sigma, spatial_sigma): a call whose two
  * sigmas differ from the previous call's rebuilds and uploads them on `stream`; such a call is refused with
  * KDE_ERR_UNSUPPORTED while `stream` is capturing (call once with the same sigmas first), as is a spatial_sigma whose
- * table would not fit (weight still non-zero after 2^20 entries on a window larger than that). */
+ * table would not fit (weight still non-zero after 2^20 entries on a window larger than that).  iteration >= 0; with
+ * iteration = 0 the cluster tables hold the sampled clusters, LD the initial grid (own cell, 999999.9) and the labels are not
+ * written, as in the reference. */
 int kde_nasp_segmentation(kde_nasp* h, const uint8_t* bgr_dev, const kde_float3* points_dev, const kde_float3* normals_dev,
                           float color_sigma, float spatial_sigma, float depth_sigma, float normal_sigma, int iteration,
                           void* stream);

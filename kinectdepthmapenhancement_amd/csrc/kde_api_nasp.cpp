@@ -131,6 +131,7 @@ extern "C" int kde_nasp_segmentation_batch(kde_nasp* h, int n, const uint8_t* bg
     a.reset_on = (depth_sigma != 0.0f || normal_sigma != 0.0f) ? 1 : 0;
     // NormalAdaptiveSuperpixel.cu:1070-1096; initLD_NASP is folded into the first calculateLD_NASP, NA5 into the sampling
     KDE_TRY(launch_nasp_sample(a, s));
+    if (iteration == 0) KDE_TRY(launch_nasp_init_ld(a, s));      // no first calculateLD_NASP to form the initial LD in
     for (int i = 0; i < iteration; i++) {
         KDE_TRY(launch_nasp_calc_ld(a, i == 0, s));
         KDE_TRY(launch_nasp_clusters(a, s));

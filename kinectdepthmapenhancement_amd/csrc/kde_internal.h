@@ -465,6 +465,7 @@ struct NaspLaunch {
     int reset_on;                  // depth_sigma != 0 || normal_sigma != 0 (.cu:349)
 };
 int launch_nasp_sample(const NaspLaunch& a, hipStream_t s);
+int launch_nasp_init_ld(const NaspLaunch& a, hipStream_t s);    // initLD_NASP alone, for iteration = 0
 int launch_nasp_calc_ld(const NaspLaunch& a, bool first, hipStream_t s);
 int launch_nasp_clusters(const NaspLaunch& a, hipStream_t s);   // analyzeClusters_NASP + calculateWeightedAverage
 

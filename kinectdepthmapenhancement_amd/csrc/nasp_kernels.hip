@@ -4,7 +4,8 @@
 //
 // Re-architecture vs the reference:
 //   initLD_NASP is folded into the first calculateLD_NASP (the previous assignment "own grid cell at 999999.9" is formed
-//      in registers), as K5 is folded into K7.
+//      in registers), as K5 is folded into K7.  A call with iteration = 0 has no first calculateLD_NASP: it runs
+//      nasp_init_ld_kernel, so that LD is what the reference's initLD_NASP leaves (labels stay as they were, as there).
 //   sampleInitialClusters_NASP: one wavefront per cluster, one candidate per lane; the 121 absolute taps (colour, normal
 //      and the tap's bad-normal test) are staged in LDS once per workgroup.
 //   calculateLD_NASP launches one 64-thread block per PIXEL in the reference; here one thread owns one pixel and walks its
@@ -143,6 +144,20 @@ __device__ __forceinline__ NaspRec make_rec(const kde_superpixel& m, const kde_f
     r.nx = n.x; r.ny = n.y; r.nz = n.z;
     r.nok = ok3_or(n) ? 1 : 0;
     return r;
+}
+
+// initLD_NASP (.cu:3-14) on its own, for a Segmentation of no iteration.  grid as nasp_calc_ld_kernel's: (ceil(W / 64),
+// ceil(H / 4), frames), one thread per pixel.
+__global__ __launch_bounds__(256) void nasp_init_ld_kernel(NaspLaunch a)
+{
+    const DaspGeom& g = a.g;
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= g.width || y >= g.height) return;
+    kde_label_distance o;
+    o.l = (y / g.wy) * g.cols + (x / g.wx);
+    o.d = 999999.9f;
+    frame_ptrs(a, blockIdx.z).ld[(size_t)y * g.width + x] = o;
 }
 
 template <bool USE_LDS, bool FIRST>
@@ -477,6 +492,15 @@ __global__ __launch_bounds__(256) void nasp_cluster_kernel(NaspLaunch a)
 int launch_nasp_sample(const NaspLaunch& a, hipStream_t s)
 {
     hipLaunchKernelGGL(nasp_sample_kernel, dim3(a.g.rows * a.g.cols, a.n), dim3(64), 0, s, a);
+    KDE_HIP_TRY(hipGetLastError());
+    return KDE_OK;
+}
+
+// initLD_NASP alone: what a Segmentation with iteration = 0 leaves in LD
+int launch_nasp_init_ld(const NaspLaunch& a, hipStream_t s)
+{
+    const dim3 grid(ceil_div(a.g.width, 64), ceil_div(a.g.height, 4), a.n);
+    hipLaunchKernelGGL(nasp_init_ld_kernel, grid, dim3(256), 0, s, a);
     KDE_HIP_TRY(hipGetLastError());
     return KDE_OK;
 }

@@ -160,6 +160,20 @@ def deep_case(seed, W, H, nc):
     return nd, labels, variance, points, size, K
 
 
+DENORMAL_TAP = F(2155.418)
+
+
+def denormal_weight_case():
+    """Found by the seeded sweep (plane_sweep `proj`, seed 3, index 0, pixel (126, 47)), here at its smallest: 3 x 1, no labels,
+    a hole on either side of one surface pixel of 2155.418 mm, window 3, depth_sigma 150.  The holes' only tap has the weight
+    exp(-2155.418^2 / 45000) * exp(-1 / 800) = 1.04 units of 2^-149: z * w rounds to 2155 units and the quotient is 2155, below
+    the only valid z of the window.  Returns (nd, labels, variance, points, size, K) and the parameters."""
+    z = np.array([0, DENORMAL_TAP, 0], F)
+    points = np.stack([np.zeros(3, F), np.zeros(3, F), z], -1)[None]
+    case = (np.zeros((1, 3, 4), F), np.full((1, 3), -1, np.int32), np.zeros(1, F), points, np.zeros(1, np.int32), np.eye(3))
+    return case, dict(window_size=3, depth_sigma=150.0)
+
+
 def golden_inputs(generate=False):
     """LabelEquivalenceSeg's four outputs from tests/golden/les_it1.npz (320 x 240, 100 superpixels), rows 60-179 and
     columns 80-239, plus the synthetic points stored in tests/golden/proj_it1.npz: on each region's plane times 1 / 1.005 /

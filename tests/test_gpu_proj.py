@@ -2,7 +2,8 @@
 tools/proj_ref.c, through the Python class.  The bar ("Plane projection (five-argument)"), every pixel checked:
 plane-fitted points bit-identical; optimized points bit-identical with window_size = 1; with the filter on <= 1e-4 relative
 with an identical zero mask where the pixel's own pre-filter z is > 50, <= 1e-4 on holes whose binary64 denominator is at
-least 2^-120, and 0 or inside the window's valid range on the rest (BAND)."""
+least 2^-120, and 0 or inside the window's valid range, widened by half a millimetre for the rounding of float32-denormal weights, on
+the rest (BAND)."""
 import numpy as np
 import pytest
 
@@ -121,6 +122,18 @@ def test_deep_case_exercises_band(T, R):
     exp, got, cmp = check(T, R, case, "deep", min_size=PC.min_size_for(70, 50))
     holes = cmp["n_hole"] + cmp["n_band"]
     assert 0 < cmp["n_band"] < holes and cmp["n_band"] < 0.05 * 70 * 50
+
+
+def test_denormal_weight_holes_stay_within_half_a_millimetre_of_their_tap(T, R):
+    """found by the seeded sweep (proj_cases.denormal_weight_case, tests/test_proj_ref.py): a hole whose only tap weighs one
+    unit of 2^-149.  The kernel's exp_denormal keeps such a weight, so the hole is filled, and what it is filled with is the
+    tap's depth to the rounding of the denormal product (the BAND bar), or 0 where hardware exp flushes the weight"""
+    case, kw = PC.denormal_weight_case()
+    exp, got, cmp = check(T, R, case, "denormal weight", **kw)
+    zg = got["optimized"][0, :, 2]
+    print("denormal weight: device", zg.tolist(), "restatement", exp["optimized"][0, :, 2].tolist())
+    assert cmp["n_band"] == 2 and zg[1] == PC.DENORMAL_TAP
+    assert all(z == 0 or abs(float(z) - float(PC.DENORMAL_TAP)) <= 0.5 for z in zg[[0, 2]])
 
 
 def test_micro_cases_inf_nan_and_table_edges(T, R):

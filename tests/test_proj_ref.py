@@ -140,6 +140,35 @@ def test_deep_case_has_a_small_band(R):
     assert float(np.nanmax(case[3][..., 2])) > 3500
 
 
+def test_denormal_weights_leave_the_window_range_by_half_a_millimetre_at_most(R):
+    """found by the seeded sweep: where a hole's tap weights are float32 denormals the reference's own arithmetic leaves
+    [min, max] of the window's valid z, so the BAND bar is that range widened by BAND_SLACK_MM (+ 2^-15 relative); the
+    restatement and the numpy transcription meet it, and half a millimetre is not more than the arithmetic needs"""
+    case, kw = PC.denormal_weight_case()
+    o = R.plane_projection(*case, **kw)
+    zo, unit = o["optimized"][0, :, 2], 2.0 ** -149
+    assert 1.0 < o["den64"][0, 0] / unit < 1.1 and o["den64"][0, 1] == 1            # one unit: the weight is the grid's 1
+    assert zo[1] == PC.DENORMAL_TAP and zo[0] == zo[2] == 2155                      # 2155 u / 1 u, below the only valid z
+    cmp = R.compare(o["plane_fitted"], o["optimized"], o, 3)
+    assert cmp["n_band"] == 2 and cmp["plane_fitted"] == cmp["strict"] == cmp["hole"] == cmp["band"] == cmp["xy"] == 0, cmp
+    n = PC.np_plane_projection(*case, **kw)
+    assert R.compare(n["plane_fitted"], n["optimized"], o, 3)["band"] == 0
+    # the interval is not a licence: a millimetre off, or the far side of the slack, still fails; 0 (every weight flushed) passes
+    for z, bad in ((2155.418 - 0.6, 1), (2155.418 + 0.6, 1), (2154.0, 1), (0.0, 0), (2155.5, 0), (2155.418, 0)):
+        g = o["optimized"].copy()
+        g[0, 0] = o["rays"][0, 0] * F(z)
+        assert R.compare(o["plane_fitted"], g, o, 3)["band"] == bad, z
+    # the bound is reached: a tap at k + 0.499 under a weight of one unit rounds down by 0.499
+    worst = 0.0
+    for zt in np.arange(2150.0, 2162.0, 0.0625, dtype=F) + F(0.499):
+        case[3][0, 1, 2] = zt
+        w = R.plane_projection(*case, **kw)
+        if 0 < w["den64"][0, 0] < 1.5 * unit:
+            worst = max(worst, abs(float(w["optimized"][0, 0, 2]) - float(zt)))
+        assert R.compare(w["plane_fitted"], w["optimized"], w, 3)["band"] == 0, zt
+    assert 0.49 < worst <= R.BAND_SLACK_MM
+
+
 def test_golden(R):
     """tests/golden/proj_it1.npz (tests/golden/make_golden_proj.py): everything before the filter to the bit; the filter's
     result to 1e-6, because it goes through libm's expf"""

@@ -22,6 +22,14 @@ DEPTH_SIGMA = np.float32(100.0)                                  # :5
 MAX_ANGLE = np.float32(3.141592653) / np.float32(8.0)            # Projection_GPU.cu:38, :203
 MIN_SIZE = 1300                                                  # :203
 BAND_DEN = 2.0 ** -120                                           # below this binary64 denominator a hole pixel is BAND
+# What the float32 quotient of a BAND pixel may lie outside [min, max] of its window's valid z by.  Below 2^-126 a weight w is
+# a whole number of units u = 2^-149 and every z * w, and every partial sum, is rounded to that grid: an error of at most u / 2
+# for each of the m taps whose weight is not 0, over a denominator of at least m u, is half a millimetre whatever the weights
+# are.  Above the grid each of the at most 15 * 15 products, the sums of both accumulators and the division round by 2^-24
+# relative: fewer than 2^9 roundings, 2^-15 of the depth.  (Found by the sweep: one tap of 2155.418 mm under a weight of one
+# unit gives 2155 u / 1 u = 2155.)
+BAND_SLACK_MM = 0.5
+BAND_SLACK_REL = 2.0 ** -15
 
 _lib = None
 
@@ -145,7 +153,7 @@ def compare(got_plane_fitted, got_optimized, exp, window_size=WINDOW_SIZE):
       plane_fitted  bit-identical (equal NaN / inf positions)
       strict        own pre-filter z > 50: <= 1e-4 relative, identical zero mask
       hole          own pre-filter z <= 50 (or NaN) and den64 >= 2^-120: <= 1e-4 relative
-      band          the rest: 0, or within [min, max] of the window's valid z
+      band          the rest: 0, or within [min, max] of the window's valid z widened by BAND_SLACK_MM + BAND_SLACK_REL * |z|
     plus the population of each class and the largest relative error seen"""
     zc, ze, zg = exp["prefilter"][..., 2], exp["optimized"][..., 2], np.asarray(got_optimized, np.float32)[..., 2]
     with np.errstate(all="ignore"):
@@ -155,7 +163,9 @@ def compare(got_plane_fitted, got_optimized, exp, window_size=WINDOW_SIZE):
         band = ~strict & (exp["den64"] < BAND_DEN)
         hole = ~strict & ~band
         mn, mx = window_range(zc, window_size)
-        in_band = (zg == 0) | ((zg >= mn) & (zg <= mx))
+        lo = mn.astype(np.float64) - (BAND_SLACK_MM + BAND_SLACK_REL * np.abs(mn.astype(np.float64)))
+        hi = mx.astype(np.float64) + (BAND_SLACK_MM + BAND_SLACK_REL * np.abs(mx.astype(np.float64)))
+        in_band = (zg == 0) | ((zg >= lo) & (zg <= hi))
         # x, y = ray * z with the GPU's own z: one float32 multiplication
         rays = exp["rays"]
         xy_bad = differing(rays[..., :2] * zg[..., None], np.asarray(got_optimized, np.float32)[..., :2]).any(-1)
