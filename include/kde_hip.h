@@ -234,10 +234,16 @@ int kde_dasp_create(kde_dasp** out, int width, int height);
 int kde_dasp_destroy(kde_dasp* h);
 /* void SetParametor(int rows, int cols, cv::Mat_<double> intrinsic) (DepthAdaptiveSuperpixel.cpp:15-39).
  * Rejects geometries the reference would index out of bounds with (KDE_ERR_INVALID):
- * width/cols >= 4, height/rows >= 4, width/(width/cols) == cols, height >= 6. */
+ * width/cols >= 4, height/rows >= 4, width/(width/cols) == cols, height >= 6.
+ * Zero-fills the cluster tables, the labels and the (distance, label) records (the reference leaves them uninitialised). */
 int kde_dasp_set_parameters(kde_dasp* h, int rows, int cols, const double* K9);
 /* void Segmentation(GpuMat color, float3* points3d, float color_sigma, float spatial_sigma,
- *                   float depth_sigma, int iteration) (DepthAdaptiveSuperpixel.cu:570-588) */
+ *                   float depth_sigma, int iteration) (DepthAdaptiveSuperpixel.cu:570-588)
+ * Domain.  The sigmas are finite and do not sum to 0; iteration >= 0.  The cloud is ANY float3 image: 0 (a hole), negative,
+ * +-inf, NaN and up to FLT_MAX depths, and x / y that project a centre anywhere, give what the reference's arithmetic gives,
+ * bit for bit -- also where a candidate distance is +inf or NaN (the 16-way tree is then evaluated literally: a NaN neither
+ * replaces nor is replaced).  iteration = 0 samples the clusters and leaves init_LD's grid (own cell, 999999.9) in the
+ * records; the labels stay what the call before left, 0 after SetParametor. */
 int kde_dasp_segmentation(kde_dasp* h, const uint8_t* bgr_dev, const kde_float3* points_dev,
                           float color_sigma, float spatial_sigma, float depth_sigma, int iteration, void* stream);
 /* int* getLabelDevice() / superpixel* getMeanDataDevice() (SuperpixelSegmentation.cpp) + DASP members */

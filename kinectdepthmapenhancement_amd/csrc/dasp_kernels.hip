@@ -19,6 +19,18 @@ namespace kde {
 namespace {
 
 // ---- K5 init_LD (.cu:3-14): folded into the first calculateLD (calc_ld_kernel<.., FIRST>) --------------
+// A Segmentation of NO iteration has no first calculateLD to fold it into: dasp_init_ld_kernel writes the grid then, so
+// that LD is what the reference's init_LD leaves (the labels stay as the call before left them, as there).
+__global__ __launch_bounds__(256) void dasp_init_ld_kernel(DaspGeom g, kde_label_distance* __restrict__ ld)
+{
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= g.width || y >= g.height) return;
+    kde_label_distance o;
+    o.l = (y / g.wy) * g.cols + (x / g.wx);
+    o.d = 999999.9f;
+    ld[(size_t)y * g.width + x] = o;
+}
 
 // ---- K6 sampleInitialClusters<16> (.cu:16-165) ---------------------------------------------------
 // A workgroup of four wavefronts serves 4 clusters x 16 candidates (one candidate per lane, as the reference's 16-thread
@@ -152,7 +164,12 @@ template <int NS>
 struct CalcSets {
     CalcSet s[NS];
     int write_ld;      // 0: the (distance, label) records are not stored (a pipeline with ONE assignment step never reads them)
+    int literal;       // 1: the weights alone can make a distance of finite terms overflow: every wavefront evaluates the tree
 };
+
+// A depth above this, of a pixel or of a cluster centre, sends the wavefront through the literal tree (see calc_ld_kernel).
+// The weights of a launch whose scan is allowed keep every distance of smaller depths finite (launch_calc_sets).
+constexpr float kScanMaxDepth = 1.0e30f;
 
 // FIRST = the assignment step that follows sampleInitialClusters: init_LD (K5) is folded in -- the previous
 // assignment is "own grid cell at distance 999999.9" and is formed in registers instead of being written by one
@@ -189,12 +206,17 @@ __global__ __launch_bounds__(256) void calc_ld_kernel(DaspGeom g, const uint8_t*
     // so mean.y can be any int above the height, INT_MAX included.  (float)(y - mean.y), which the reference forms
     // (.cu:213), equals (float)y - (float)mean.y only while both fit a float exactly: a table that holds such a
     // coordinate (|v| >= 2^24) switches the workgroup to the integer subtraction and the library sqrtf.
-    __shared__ int s_big;
+    __shared__ int s_big, s_far;
     bool big = !USE_LDS;              // the table-in-global form always subtracts integers
+    // a centre depth that is not < kScanMaxDepth (+inf, 3e38, NaN) is in the table, or the launch's weights overflow
+    bool far_table = sets.literal != 0;
     if (USE_LDS) {
-        if (threadIdx.x == 0) s_big = 0;
+        if (threadIdx.x == 0) {
+            s_big = 0;
+            s_far = sets.literal;
+        }
         __syncthreads();
-        bool mine = false;
+        bool mine = false, mine_far = false;
 #pragma unroll
         for (int n = 0; n < NTAB; n++)
             for (int i = threadIdx.x; i < nclusters; i += 256) {
@@ -209,11 +231,14 @@ __global__ __launch_bounds__(256) void calc_ld_kernel(DaspGeom g, const uint8_t*
                 r.xi = m.x;
                 r.yi = m.y;
                 mine |= m.x >= (1 << 24) || m.x <= -(1 << 24) || m.y >= (1 << 24) || m.y <= -(1 << 24);
+                mine_far |= !(r.cz < kScanMaxDepth);
                 recs[n * nclusters + i] = r;
             }
         if (mine) s_big = 1;
+        if (mine_far) s_far = 1;
         __syncthreads();
         big = s_big != 0;             // workgroup-uniform
+        far_table = s_far != 0;
     }
     const int x = blockIdx.x * 64 + (threadIdx.x & 63);
     const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
@@ -255,6 +280,11 @@ __global__ __launch_bounds__(256) void calc_ld_kernel(DaspGeom g, const uint8_t*
     // a 1e-5 margin; colour and depth terms are >= 0) can neither win nor tie.  The skip is taken when no lane of
     // the wavefront needs the candidate; typically 5 of 16 are evaluated.  Segmenters lo..hi share table `tab` and
     // the previous assignment `cur` (all of them in the FIRST step, one at a time later).
+    // That holds while every candidate distance is finite.  The tree starts from candidate 0, not from +inf, and a NaN in
+    // it neither replaces nor is replaced: it can shadow its right sibling, a candidate the scan would have skipped
+    // included.  So a wavefront in which a distance can be +inf or NaN -- a pixel or centre depth that is not below
+    // kScanMaxDepth, a previous distance that is not finite, weights that overflow (sets.literal) -- evaluates the tree
+    // LITERALLY instead (assign_literal), as nasp_kernels.hip does; on finite distances the two are the same function.
     // inner = every lane's 4 x 4 candidate block lies inside the cluster grid (wavefront-uniform, std::true_type /
     // std::false_type): no candidate can be "outside the grid", so its tests and selects are not even compiled in
     auto assign_impl = [&](auto inner, int tab, int lo, int hi, const kde_label_distance cur, int ccx, int ccy) {
@@ -342,11 +372,71 @@ __global__ __launch_bounds__(256) void calc_ld_kernel(DaspGeom g, const uint8_t*
             cs.labels[p] = o.l;
         }
     };
+    // The reference's tree on all 16 candidates, depth first: the leaves in bit-reversed order, finished sub-trees combined
+    // as a binary counter carries (a stack of five (distance, label) pairs) -- the same 15 comparisons on the same operands.
+    // One segmenter at a time, so that the stack costs the scan's wavefronts no registers.
+    auto assign_literal = [&](int tab, int lo, int hi, const kde_label_distance cur, int ccx, int ccy) {
+#pragma unroll
+        for (int n = 0; n < NS; n++) {
+            if (n < lo || n > hi) continue;
+            const CalcSet& cs = sets.s[n];
+            float sd[5];
+            int sl[5];
+#pragma unroll
+            for (int k = 0; k < 16; k++) {
+                const int t = ((k & 1) << 3) | ((k & 2) << 1) | ((k & 4) >> 1) | ((k & 8) >> 3);
+                const int rx = ccx - 2 + (t & 3), ry = ccy - 2 + (t >> 2);
+                const int id = (rx >= 0 && rx < g.cols && ry >= 0 && ry < g.rows) ? ry * g.cols + rx : -1;
+                float cdv = 0.0f, sdv = 0.0f, ddv = 0.0f;
+                if (id >= 0) candidate(tab, id, cdv, sdv, ddv);
+                float d = id >= 0 ? cdv * cs.kc + sdv * cs.ks + ddv * cs.kd : cur.d;     // .cu:218, :221-224
+                int l = id >= 0 ? id : cur.l;
+                int j = 0;
+#pragma unroll
+                for (; (k >> j) & 1; j++) {           // left = the finished sub-tree, right = this one: left > right ? right : left
+                    const bool right = sd[j] > d;
+                    d = right ? d : sd[j];
+                    l = right ? l : sl[j];
+                }
+                sd[j] = d;
+                sl[j] = l;
+            }
+            kde_label_distance o;
+            o.l = sl[4];
+            o.d = sd[4];
+            if (z < 50.0f && cs.depth_on) {   // .cu:308-312
+                o.l = -1;
+                o.d = 0.0f;
+            }
+            if (sets.write_ld) cs.ld[p] = o;
+            cs.labels[p] = o.l;
+        }
+    };
     // (ccx, ccy) = the grid cell of the previous assignment: cur.l % cols, cur.l / cols
     auto assign = [&](int tab, int lo, int hi, const kde_label_distance cur, int ccx, int ccy) {
+        // The table's part of the condition is known before anything is loaded; the pixel's own depth is tested AFTER the
+        // scan, whose stores the literal tree then overwrites: the scan does not wait for the cloud before it starts, and
+        // a wavefront with such a pixel is rare.
+        bool far = far_table;
+        if (!USE_LDS) {                   // no staged table to have looked through: the 16 candidates' own centres
+            bool mine = false;
+#pragma unroll
+            for (int t = 0; t < 16; t++) {
+                const int rx = ccx - 2 + (t & 3), ry = ccy - 2 + (t >> 2);
+                if (rx >= 0 && rx < g.cols && ry >= 0 && ry < g.rows) mine |= !(sets.s[tab].centers[ry * g.cols + rx].z < kScanMaxDepth);
+            }
+            far = far || __builtin_amdgcn_ballot_w64(mine) != 0;
+        }
         const bool in = cur.l >= 0 && ccx >= 2 && ccx + 1 < g.cols && ccy >= 2 && ccy + 1 < g.rows;
-        if (__builtin_amdgcn_ballot_w64(!in) == 0) assign_impl(std::true_type{}, tab, lo, hi, cur, ccx, ccy);
-        else assign_impl(std::false_type{}, tab, lo, hi, cur, ccx, ccy);
+        const bool inner = __builtin_amdgcn_ballot_w64(!in) == 0;
+        // only a candidate outside the grid carries the previous distance (.cu:221-224): tested where one can exist
+        if (!inner) far = far || __builtin_amdgcn_ballot_w64(!(cur.d < INFINITY)) != 0;
+        if (!far) {
+            if (inner) assign_impl(std::true_type{}, tab, lo, hi, cur, ccx, ccy);
+            else assign_impl(std::false_type{}, tab, lo, hi, cur, ccx, ccy);
+            far = __builtin_amdgcn_ballot_w64(!(z < kScanMaxDepth)) != 0;
+        }
+        if (__builtin_expect(far, 0)) assign_literal(tab, lo, hi, cur, ccx, ccy);
     };
 
     if (FIRST) {
@@ -549,11 +639,20 @@ static CalcSet make_set(const DaspGeom& g, kde_label_distance* ld, const kde_sup
 }
 
 template <int NS>
-static int launch_calc_sets(const DaspGeom& g, int n, const uint8_t* bgr, const kde_float3* pts, const CalcSets<NS>& sets,
+static int launch_calc_sets(const DaspGeom& g, int n, const uint8_t* bgr, const kde_float3* pts, CalcSets<NS> sets,
                             bool first, hipStream_t s)
 {
     const float half = (float)(g.wx + g.wy) / 2.0f;
     const float win2 = half * half;
+    // The scan of calc_ld_kernel needs finite distances.  With depths below kScanMaxDepth the three terms are at most
+    // 3 * 255^2, sqrt(2) * 2^32 * win2 (integer offsets that wrap) and kScanMaxDepth: weights under which their weighted sum
+    // stays two decades below FLT_MAX allow it; any other weights (a sigma sum near 0: the weights are squares of
+    // sigma / sum, so the sign of a sigma matters through the sum alone) do not.
+    sets.literal = 0;
+    for (int k = 0; k < NS; k++) {
+        const double top = 195075.0 * sets.s[k].kc + 6.08e9 * (double)win2 * sets.s[k].ks + (double)kScanMaxDepth * sets.s[k].kd;
+        if (!(top < 1.0e36)) sets.literal = 1;
+    }
     const int nclusters = g.rows * g.cols;
     const int tables = first ? 1 : NS;
     const bool lds = tables * nclusters <= kMaxLdsClusters;
@@ -570,6 +669,14 @@ static int launch_calc_sets(const DaspGeom& g, int n, const uint8_t* bgr, const 
         if (lds) hipLaunchKernelGGL((calc_ld_kernel<NS, true, false>), grid, dim3(256), bytes, s, g, bgr, pts, sets, win2, dv);
         else hipLaunchKernelGGL((calc_ld_kernel<NS, false, false>), grid, dim3(256), 0, s, g, bgr, pts, sets, win2, dv);
     }
+    KDE_HIP_TRY(hipGetLastError());
+    return KDE_OK;
+}
+
+// init_LD alone, for a Segmentation of no iteration (one frame: the public segmenter; the pipelines' counts are positive)
+int launch_dasp_init_ld(const DaspGeom& g, kde_label_distance* ld, hipStream_t s)
+{
+    hipLaunchKernelGGL(dasp_init_ld_kernel, dim3(ceil_div(g.width, 64), ceil_div(g.height, 4)), dim3(256), 0, s, g, ld);
     KDE_HIP_TRY(hipGetLastError());
     return KDE_OK;
 }

@@ -36,6 +36,10 @@ extern "C" int kde_dasp_set_parameters(kde_dasp* h, int rows, int cols, const do
     KDE_TRY(h->centers.alloc(k));
     KDE_HIP_TRY(hipMemset(h->mean.p, 0, k * sizeof(kde_superpixel)));
     KDE_HIP_TRY(hipMemset(h->centers.p, 0, k * sizeof(kde_float3)));
+    // what a call of no iteration leaves where the reference's buffers are uninitialised: labels 0 (and LD 0 until a call)
+    const size_t px = (size_t)h->width * h->height * h->max_batch;
+    KDE_HIP_TRY(hipMemset(h->ld.p, 0, px * sizeof(kde_label_distance)));
+    KDE_HIP_TRY(hipMemset(h->labels.p, 0, px * sizeof(int32_t)));
     float intr[9];
     for (int i = 0; i < 9; i++) intr[i] = (float)K[i];   // DepthAdaptiveSuperpixel.cpp:33-37
     KDE_HIP_TRY(hipMemcpy(h->intr.p, intr, sizeof(intr), hipMemcpyHostToDevice));
@@ -57,6 +61,7 @@ extern "C" int kde_dasp_segmentation(kde_dasp* h, const uint8_t* bgr_dev, const 
     // DepthAdaptiveSuperpixel.cu:570-586
     // init_LD (K5) is folded into the first calculateLD: its output is only ever read there
     KDE_TRY(launch_dasp_sample(h->g, 1, bgr_dev, points_dev, h->mean.p, h->centers.p, nullptr, nullptr, s));
+    if (iteration == 0) KDE_TRY(launch_dasp_init_ld(h->g, h->ld.p, s));      // no first calculateLD to form the initial LD in
     for (int i = 0; i < iteration; i++) {
         KDE_TRY(launch_dasp_calc_ld(h->g, bgr_dev, points_dev, h->ld.p, h->mean.p, h->centers.p, h->labels.p,
                                     color_sigma, spatial_sigma, depth_sigma, i == 0, s));

@@ -450,13 +450,23 @@ def intr9(K):
     return np.ascontiguousarray(np.asarray(K, np.float64).reshape(9).astype(np.float32))
 
 
-def dasp_segmentation(bgr, points, rows, cols, K, color_sigma, spatial_sigma, depth_sigma, iteration):
+def _tables(rows, cols, mean, centers):
+    """the cluster tables a call starts from: zeros (what SetParametor leaves), or copies of what the call before left -- the
+    object keeps its tables, and neither sampleInitialClusters nor analyzeClusters writes every field of every cluster"""
+    m = np.zeros(rows * cols, SUPERPIXEL) if mean is None else np.ascontiguousarray(mean, SUPERPIXEL).copy()
+    c = np.zeros(rows * cols, FLOAT3) if centers is None else np.ascontiguousarray(centers, FLOAT3).copy()
+    assert m.shape == c.shape == (rows * cols,)
+    return m, c
+
+
+def dasp_segmentation(bgr, points, rows, cols, K, color_sigma, spatial_sigma, depth_sigma, iteration, mean=None, centers=None):
+    """mean / centers: the tables of the call before on the same object (None: a fresh object).  With iteration = 0 the labels
+    are not written by the reference: the returned map is uninitialised memory and means nothing."""
     bgr, pts = _u8(bgr), _pts(points)
     h, w = pts.shape
     labels = np.empty((h, w), np.int32)
     ld = np.empty((h, w), LABEL_DISTANCE)
-    mean = np.zeros(rows * cols, SUPERPIXEL)
-    centers = np.zeros(rows * cols, FLOAT3)
+    mean, centers = _tables(rows, cols, mean, centers)
     k = intr9(K)
     rc = lib().okde_dasp_segmentation(w, h, rows, cols, _p(k), _p(bgr), _p(pts),
                                       C.c_float(color_sigma), C.c_float(spatial_sigma),
@@ -467,13 +477,13 @@ def dasp_segmentation(bgr, points, rows, cols, K, color_sigma, spatial_sigma, de
     return labels, ld, mean, centers
 
 
-def dasp_steps(bgr, points, rows, cols):
-    """init_LD + sampleInitialClusters only (for unit tests of the individual kernels)."""
+def dasp_steps(bgr, points, rows, cols, mean=None, centers=None):
+    """init_LD + sampleInitialClusters only (for unit tests of the individual kernels, and what a Segmentation of no iteration
+    does); mean / centers as in dasp_segmentation."""
     bgr, pts = _u8(bgr), _pts(points)
     h, w = pts.shape
     ld = np.empty((h, w), LABEL_DISTANCE)
-    mean = np.zeros(rows * cols, SUPERPIXEL)
-    centers = np.zeros(rows * cols, FLOAT3)
+    mean, centers = _tables(rows, cols, mean, centers)
     lib().okde_dasp_init_ld(w, h, rows, cols, _p(ld))
     lib().okde_dasp_sample_clusters(w, h, rows, cols, _p(bgr), _p(pts), _p(mean), _p(centers))
     return ld, mean, centers
