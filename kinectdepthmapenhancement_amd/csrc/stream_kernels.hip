@@ -197,9 +197,12 @@ __device__ __forceinline__ void update_weighted_depth(float& rd, float& rw, floa
     // updateWaitedDepth, ArrayBuffer/Buffer2D.cu:13-30
     if (d > 50.0f) {
         if (rd != 0.0f) {
-            int diff = f2i_rz(rd) - f2i_rz(d);
-            if (diff < 0) diff = -diff;
-            if ((float)diff < d * 0.01f) {
+            // abs() as the reference's: the difference wraps and INT_MIN stays INT_MIN (a negative float).  Written on
+            // unsigned as in update_pair: on int both are undefined, and the compiler converts the "non-negative" result
+            // as unsigned, which turns INT_MIN into +2^31
+            const unsigned diff = (unsigned)f2i_rz(rd) - (unsigned)f2i_rz(d);
+            const int ad = (int)diff < 0 ? (int)(0u - diff) : (int)diff;
+            if ((float)ad < d * 0.01f) {
                 rd = ((rd * (rw + 1.0f)) + (d * rw)) / (rw * 2.0f + 1.0f);
                 rw = rw + 1.0f;
             }

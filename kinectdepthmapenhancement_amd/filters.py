@@ -331,8 +331,9 @@ class DimensionConvertor(_Handle):
         return n
 
     def projectiveToReal(self, data: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
-        """both overloads: float* depth -> float3* (DimensionConvertor.cu:3-23) or float3* -> float3* (:25-33)."""
-        if data.shape[-1] == 3 and data.dim() >= 3 and tuple(data.shape[-3:-1]) == (self.Height, self.Width):
+        """both overloads: float* depth -> float3* (DimensionConvertor.cu:3-23) or float3* -> float3* (:25-33).  The float3
+        overload is the one whose `out` has the rank of `data`: three depth frames of 3 x 3 have the shape of one 3 x 3 cloud."""
+        if data.shape[-1] == 3 and data.dim() >= 3 and tuple(data.shape[-3:-1]) == (self.Height, self.Width) and out.dim() == data.dim():
             n = self._n(data, (3,))
             self._n(out, (3,))
             check(lib().kde_dimconv_projective_to_real_points(self._h, n, data.data_ptr(), out.data_ptr(), _stream()))

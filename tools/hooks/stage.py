@@ -126,43 +126,55 @@ def ers_stage_run(color_labels, depth_labels, depth, bgr, variant=0, force_full_
     return res
 
 
+def spdsr_tail_calls(width, height, rows, cols, K, calls, max_batch):
+    """kde_stage_spdsr_tail (include/kde_test_hooks.h), the calls in order on ONE fresh SPDepthSuperResolution handle of the stage
+    build.  A call is a dict: labels [n,H,W] int32, points [n,H,W,3] float32, nd None (fit the planes) or [n,k,4] float32 (use
+    these), sweeps.  -> per call (nd [n,k,4], plane_fitted [n,H,W,3], optimized [n,H,W,3]) numpy, as the handle held them after
+    that call (a marker (5,5,5) keeps the w the frame slot held before it)."""
+    import numpy as np
+    import torch
+    from kinectdepthmapenhancement_amd import _native, filters
+    t = lambda a: torch.from_numpy(a).cuda()
+    k, out = rows * cols, []
+    with stage_library():
+        sp = filters.SPDepthSuperResolution(width, height, max_batch=max_batch)
+        try:
+            sp.SetParametor(rows, cols, K)
+            for call in calls:
+                lab = np.ascontiguousarray(call["labels"], np.int32).reshape((-1, height, width))
+                n = lab.shape[0]
+                pts = np.ascontiguousarray(call["points"], np.float32).reshape((n, height, width, 3))
+                planes = call.get("nd")
+                # the tensors stay referenced until the synchronize below
+                args = [t(lab), t(pts)] + ([t(np.ascontiguousarray(planes, np.float32).reshape((n, k, 4)))] if planes is not None else [])
+                _native.check(lib().kde_stage_spdsr_tail(sp._h, n, args[0].data_ptr(), args[1].data_ptr(),
+                                                         args[2].data_ptr() if planes is not None else None, call["sweeps"], filters._stream()))
+                sp._n = n
+                torch.cuda.synchronize()
+                out.append((sp.getClusterND_Device().cpu().numpy().reshape((n, k, 4)).copy(),
+                            sp.getPlaneFitted3D_Device().cpu().numpy().reshape((n, height, width, 3)).copy(),
+                            sp.getOptimizedPoints_Device().cpu().numpy().reshape((n, height, width, 3)).copy()))
+        finally:
+            sp.close()
+    return out
+
+
 def spdsr_tail_run(width, height, rows, cols, K, labels, points, nd=None, sweeps=20, max_batch=None, nd_prev_call=None):
-    """kde_stage_spdsr_tail (include/kde_test_hooks.h) on a fresh SPDepthSuperResolution handle of the stage build:
+    """spdsr_tail_calls for one call on a fresh handle:
     labels [H,W] or [n,H,W] int32, points [...,3] float32, nd None (fit the planes) or [k,4] / [n,k,4] float32 (use these).
     nd_prev_call = {"labels": ..., "points": ...} of a first call on the SAME handle with the planes fitted and no sweeps;
     its planes are stored under nd_prev_call["nd"] (the (5,5,5) marker of the second call keeps that call's w).
     -> (nd, plane_fitted, optimized) numpy, with a leading n only when labels has one."""
     import numpy as np
-    import torch
-    from kinectdepthmapenhancement_amd import _native, filters
     lab = np.ascontiguousarray(labels, np.int32)
     batched = lab.ndim == 3
     lab = lab.reshape((-1, height, width))
     n = lab.shape[0]
-    pts = np.ascontiguousarray(points, np.float32).reshape((n, height, width, 3))
-    t = lambda a: torch.from_numpy(a).cuda()
-
-    def call(sp, l, p, planes, k, sw):
-        # the tensors stay referenced until the synchronize below
-        args = [t(l), t(p)] + ([t(np.ascontiguousarray(planes, np.float32).reshape((k, rows * cols, 4)))] if planes is not None else [])
-        _native.check(lib().kde_stage_spdsr_tail(sp._h, k, args[0].data_ptr(), args[1].data_ptr(),
-                                                 args[2].data_ptr() if planes is not None else None, sw, filters._stream()))
-        sp._n = k
-        torch.cuda.synchronize()
-
-    with stage_library():
-        sp = filters.SPDepthSuperResolution(width, height, max_batch=n if max_batch is None else max_batch)
-        try:
-            sp.SetParametor(rows, cols, K)
-            if nd_prev_call is not None:
-                l0 = np.ascontiguousarray(nd_prev_call["labels"], np.int32).reshape((-1, height, width))
-                call(sp, l0, np.ascontiguousarray(nd_prev_call["points"], np.float32).reshape(l0.shape + (3,)), None, l0.shape[0], 0)
-                nd_prev_call["nd"] = sp.getClusterND_Device().cpu().numpy().reshape((-1, rows * cols, 4))[0 if l0.shape[0] == 1 else slice(None)]
-            call(sp, lab, pts, nd, n, sweeps)
-            res = [sp.getClusterND_Device().cpu().numpy(), sp.getPlaneFitted3D_Device().cpu().numpy(),
-                   sp.getOptimizedPoints_Device().cpu().numpy()]
-        finally:
-            sp.close()
-    if n == 1:      # the getters drop the leading 1
-        res = [r[None] for r in res]
-    return tuple(r if batched else r[0] for r in res)
+    calls = [dict(labels=lab, points=points, nd=nd, sweeps=sweeps)]
+    if nd_prev_call is not None:
+        calls.insert(0, dict(labels=nd_prev_call["labels"], points=nd_prev_call["points"], nd=None, sweeps=0))
+    res = spdsr_tail_calls(width, height, rows, cols, K, calls, n if max_batch is None else max_batch)
+    if nd_prev_call is not None:
+        first = res[0][0]
+        nd_prev_call["nd"] = first[0] if first.shape[0] == 1 else first
+    return tuple(r if batched else r[0] for r in res[-1])
