@@ -1205,6 +1205,101 @@ private:
     void* stream_ = nullptr;
 };
 
+// extension (no reference counterpart as a class): the surface of main.cpp:211-300 as a triangle mesh of the organised grid,
+// for n frames of one method on the device (kde_mesh_*).  The vertices are exactly PointCloudXYZRGB's dense cloud, the vertex
+// index of a valid pixel its rank in raster order; a pixel quad gives 0, 1 or 2 triangles (kde_mesh_triangle, three indices),
+// a triangle iff its corners are valid and its edges linked, |za - zb| <= max_diff + rel_diff * min(za, zb).  Triangles are
+// ordered by owning pixel; frame f's are the first tri_counts[f] records of its slot of 2 (W - 1) (H - 1).  build() is
+// asynchronous on the object's stream and capturable; the *_Host members synchronise.  include/kde/ply_io.hpp writes the
+// mesh as a PLY file.
+class OrganizedMesh {
+public:
+    static kde_mesh_params defaultParams()
+    {
+        kde_mesh_params p{};
+        check(kde_mesh_default_params(&p));
+        return p;
+    }
+    OrganizedMesh(int width, int height, int max_batch = 1) { check(kde_mesh_create(&h_, width, height, max_batch, nullptr)); }
+    OrganizedMesh(int width, int height, int max_batch, const kde_mesh_params& params)
+    {
+        check(kde_mesh_create(&h_, width, height, max_batch, &params));
+    }
+    ~OrganizedMesh() { kde_mesh_destroy(h_); }
+    OrganizedMesh(const OrganizedMesh&) = delete;
+    OrganizedMesh& operator=(const OrganizedMesh&) = delete;
+
+    template <class MatLike>
+    void setCamera(const MatLike& intrinsic)
+    {
+        double k[9];
+        intrinsic_to_array(intrinsic, k);
+        check(kde_mesh_set_camera(h_, k));
+    }
+    // n frames of `source` with bgr_frames = 1 (one image for every frame) or n packed BGR images; an output that is nullptr
+    // is the object-owned buffer
+    void build(int n, const kde_error3d_source& source, const uint8_t* bgr_device, int bgr_frames = 1,
+               kde_cloud_point* vertices_device = nullptr, kde_mesh_triangle* triangles_device = nullptr)
+    {
+        check(kde_mesh_build_batch(h_, n, &source, bgr_device, bgr_frames, vertices_device, triangles_device, stream_));
+    }
+    kde_cloud_point* vertices_Device() const
+    {
+        kde_cloud_point* p = nullptr;
+        check(kde_mesh_vertices_device(h_, &p));
+        return p;
+    }
+    kde_mesh_triangle* triangles_Device() const
+    {
+        kde_mesh_triangle* p = nullptr;
+        check(kde_mesh_triangles_device(h_, &p));
+        return p;
+    }
+    uint32_t* counts_Device() const
+    {
+        uint32_t* p = nullptr;
+        check(kde_mesh_counts_device(h_, &p));
+        return p;
+    }
+    uint32_t* triCounts_Device() const
+    {
+        uint32_t* p = nullptr;
+        check(kde_mesh_tri_counts_device(h_, &p));
+        return p;
+    }
+    const uint32_t* counts_Host() const
+    {
+        const uint32_t* p = nullptr;
+        check(kde_mesh_counts_host(h_, stream_, &p));
+        return p;
+    }
+    const uint32_t* triCounts_Host() const
+    {
+        const uint32_t* p = nullptr;
+        check(kde_mesh_tri_counts_host(h_, stream_, &p));
+        return p;
+    }
+    // the frames packed tightly: frame f is the records offsets[f] .. offsets[f + 1] - 1
+    const kde_cloud_point* vertices_Host(const uint64_t** offsets) const
+    {
+        const kde_cloud_point* p = nullptr;
+        check(kde_mesh_vertices_host(h_, stream_, &p, offsets));
+        return p;
+    }
+    const kde_mesh_triangle* triangles_Host(const uint64_t** offsets) const
+    {
+        const kde_mesh_triangle* p = nullptr;
+        check(kde_mesh_triangles_host(h_, stream_, &p, offsets));
+        return p;
+    }
+    void setStream(void* hip_stream) { stream_ = hip_stream; }
+    kde_mesh* handle() const { return h_; }
+
+private:
+    kde_mesh* h_ = nullptr;
+    void* stream_ = nullptr;
+};
+
 namespace detail {
 // What the depth-in / depth-out stage classes below share (csrc/kde_depth_stage.h is the same core in the library): the handle
 // and its stream, the results of the last batch call on the device and in pinned memory, and the format of a depth pointer.

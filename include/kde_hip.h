@@ -668,6 +668,67 @@ int kde_cloud_counts_host(kde_cloud* h, void* stream, const uint32_t** out);
 int kde_cloud_points_host(kde_cloud* h, void* stream, const kde_cloud_point** out, const uint64_t** offsets);
 
 /* ==========================================================================================
+ * OrganizedMesh: the surface main.cpp:211-300 hands to its viewer as points, as a triangle mesh of the organised grid, for a
+ * batch of frames (the reference has no mesh; it stands in for pcl::OrganizedFastMesh on the cloud of main.cpp:211-300).
+ * One frame has W x H pixels, W, H >= 2; a source is what kde_error3d_source describes, projected as kde_cloud_* projects it.
+ *   vertices   exactly the dense cloud: pixel i is a vertex iff p.z > z_min && p.z < z_max; its record is the kde_cloud_point
+ *              of kde_cloud_build_batch (same divisor, negate_z), stored in raster order in the frame's slot, which starts
+ *              at record f * W * H; count[f] of them, nothing written behind.  The index of a vertex is its rank.
+ *   edges      two pixels are linked iff both are valid and |za - zb| <= max_diff + rel_diff * min(za, zb), z the source's z
+ *              in millimetres; one subtraction, one product, one sum in binary32 (the link of kde_speckle_*)
+ *   triangles  pixel (x, y), x < W - 1, y < H - 1, owns the quad a = (x, y), b = (x + 1, y), c = (x, y + 1), d = (x + 1, y + 1).
+ *              A triangle is emitted iff its three corners are valid and its three edges linked.  Four valid corners:
+ *              KDE_MESH_DIAG_AD gives (a, c, d) then (a, d, b); KDE_MESH_DIAG_BC (a, c, b) then (b, c, d);
+ *              KDE_MESH_DIAG_ADAPTIVE cuts along b-c iff |zb - zc| < |za - zd| (a tie goes to a-d).  Each of the two is
+ *              tested on its own; the other cut is not tried.  Exactly three valid corners: a missing (b, c, d), b missing
+ *              (a, c, d), c missing (a, d, b), d missing (a, c, b).  All turn the same way in the image; flip_winding swaps
+ *              v1 and v2 of every triangle.
+ *   records    kde_mesh_triangle, 12 bytes, frame-local indices, ordered by owning pixel in raster order, within a quad the
+ *              first before the second: the first tri_count[f] records of the slot that starts at record
+ *              f * 2 (W - 1) (H - 1); nothing written behind.
+ * The result is a function of the frame alone: the same bytes for any batch, place in it and pointer alignment.
+ * ========================================================================================== */
+enum { KDE_MESH_DIAG_AD = 0, KDE_MESH_DIAG_BC = 1, KDE_MESH_DIAG_ADAPTIVE = 2 };
+typedef struct kde_mesh_triangle { uint32_t v0, v1, v2; } kde_mesh_triangle;                 /* 12 bytes */
+typedef struct kde_mesh_params {
+    float z_min, z_max, divisor; int negate_z; float max_diff, rel_diff; int diagonal; int flip_winding;
+} kde_mesh_params;
+typedef struct kde_mesh kde_mesh;
+/* the literals of main.cpp:211-300 (50, 15000, 1000, negate_z 1), the link of kde_speckle_default_params (10, 0.02),
+ * KDE_MESH_DIAG_ADAPTIVE, flip_winding 0 */
+int kde_mesh_default_params(kde_mesh_params* p);
+/* the surface of main.cpp:211-300 for max_batch frames on the current device; p == NULL: the defaults.  width, height >= 2;
+ * z_min, z_max, divisor as kde_cloud_create; max_diff, rel_diff finite and >= 0; diagonal in 0..2.  The object owns
+ * max_batch * W * H vertex records and max_batch * 2 (W - 1) (H - 1) triangle records for calls with NULL outputs.  On a host
+ * without a device the object is created without buffers and kde_mesh_build_batch returns KDE_ERR_HIP, like kde_cloud_create. */
+int kde_mesh_create(kde_mesh** out, int width, int height, int max_batch, const kde_mesh_params* p);
+int kde_mesh_destroy(kde_mesh* h);   /* main.cpp:211-300 holds its clouds in shared pointers; NULL is a no-op */
+/* the camera a depth-map source is projected with (main.cpp:211-300 reads clouds made by convertor.projectiveToReal, :168),
+ * as kde_cloud_set_camera.  Needed only when the source is a depth map. */
+int kde_mesh_set_camera(kde_mesh* h, const double* K9);
+/* the loop of main.cpp:211-300 for n <= max_batch frames, with the triangles: src, bgr_dev and bgr_frames as
+ * kde_cloud_build_batch; vertices_out_dev is [n][W * H] records on a 16-byte boundary, triangles_out_dev
+ * [n][2 (W - 1) (H - 1)] records on a 4-byte boundary, either NULL for the object-owned buffer.  Six launches (the three of the
+ * dense cloud, classify, scan, emit), no memset, no allocation, no upload, no host synchronisation, no spinning between
+ * workgroups: capturable from the first call. */
+int kde_mesh_build_batch(kde_mesh* h, int n, const kde_error3d_source* src, const uint8_t* bgr_dev, int bgr_frames,
+                         kde_cloud_point* vertices_out_dev, kde_mesh_triangle* triangles_out_dev, void* stream);
+/* the records of the last call of main.cpp:211-300's loop (the outputs of that call, or the object-owned buffers), count[n]
+ * and tri_count[n]; valid until the next call or destroy.  KDE_ERR_INVALID before the first call. */
+int kde_mesh_vertices_device(kde_mesh* h, kde_cloud_point** out);
+int kde_mesh_triangles_device(kde_mesh* h, kde_mesh_triangle** out);   /* main.cpp:211-300 has no faces: the triangles of the last call */
+int kde_mesh_counts_device(kde_mesh* h, uint32_t** out);       /* main.cpp:211-300: the sizes of its clouds, on the device */
+int kde_mesh_tri_counts_device(kde_mesh* h, uint32_t** out);   /* main.cpp:211-300 has no faces: their number per frame, on the device */
+/* count[n] / tri_count[n] in pinned host memory after a blocking copy on `stream` (main.cpp:211-300: cloud->size()): synchronise */
+int kde_mesh_counts_host(kde_mesh* h, void* stream, const uint32_t** out);
+int kde_mesh_tri_counts_host(kde_mesh* h, void* stream, const uint32_t** out);   /* main.cpp:211-300: the number of faces, as cloud->size() */
+/* the vertices / triangles of main.cpp:211-300's surface in pinned host memory (allocated on first use), frames packed
+ * tightly: frame f is the records offsets[f] .. offsets[f + 1] - 1, offsets[n] the total; only the used records are copied.
+ * The output buffers of the last call must still be alive.  Synchronise, like kde_cloud_points_host. */
+int kde_mesh_vertices_host(kde_mesh* h, void* stream, const kde_cloud_point** out, const uint64_t** offsets);
+int kde_mesh_triangles_host(kde_mesh* h, void* stream, const kde_mesh_triangle** out, const uint64_t** offsets);   /* main.cpp:211-300 */
+
+/* ==========================================================================================
  * DepthRegistration: depth warped into the colour camera's view.  Every class of this library assumes that depth pixel
  * (x, y) and colour pixel (x, y) look along the same ray; the reference gets that from outside its own code:
  * Kinect::InitAllData (Kinect.cpp:71-75) asks OpenNI to register the depth stream to the image stream before any frame

@@ -95,6 +95,26 @@ class CloudPoint(C.Structure):
     _fields_ = [("x", C.c_float), ("y", C.c_float), ("z", C.c_float), ("rgb", C.c_uint32)]
 
 
+KDE_MESH_DIAG_AD, KDE_MESH_DIAG_BC, KDE_MESH_DIAG_ADAPTIVE = 0, 1, 2
+
+
+class MeshHandle(C.c_void_p):
+    """kde_mesh*: a ctypes type of its own, like CloudHandle, which keeps the kde_mesh_* entry points out of the frozen
+    record tools/abi_refusals.py enumerates; tests/test_mesh_abi.py checks their refusals."""
+
+
+class MeshParams(C.Structure):
+    """kde_mesh_params (defaults = the cloud's 50, 15000, 1000, negated z; the speckle filter's link 10, 0.02; the adaptive
+    cut; winding as it is)."""
+    _fields_ = [("z_min", C.c_float), ("z_max", C.c_float), ("divisor", C.c_float), ("negate_z", C.c_int),
+                ("max_diff", C.c_float), ("rel_diff", C.c_float), ("diagonal", C.c_int), ("flip_winding", C.c_int)]
+
+
+class MeshTriangle(C.Structure):
+    """kde_mesh_triangle (12 bytes): three frame-local vertex indices."""
+    _fields_ = [("v0", C.c_uint32), ("v1", C.c_uint32), ("v2", C.c_uint32)]
+
+
 class RegHandle(C.c_void_p):
     """kde_reg*: a ctypes type of its own, like CloudHandle, which keeps the kde_reg_* entry points out of the frozen record
     tools/abi_refusals.py enumerates; tests/test_reg_abi.py checks their refusals."""
@@ -359,6 +379,19 @@ SIGNATURES = {
     "kde_cloud_counts_device": (_i, [CloudHandle, _pp]),
     "kde_cloud_counts_host": (_i, [CloudHandle, _vp, _pp]),
     "kde_cloud_points_host": (_i, [CloudHandle, _vp, _pp, _pp]),
+    "kde_mesh_default_params": (_i, [C.POINTER(MeshParams)]),
+    "kde_mesh_create": (_i, [C.POINTER(MeshHandle), _i, _i, _i, C.POINTER(MeshParams)]),
+    "kde_mesh_destroy": (_i, [MeshHandle]),
+    "kde_mesh_set_camera": (_i, [MeshHandle, _vp]),
+    "kde_mesh_build_batch": (_i, [MeshHandle, _i, C.POINTER(Error3dSource), _vp, _i, _vp, _vp, _vp]),
+    "kde_mesh_vertices_device": (_i, [MeshHandle, _pp]),
+    "kde_mesh_triangles_device": (_i, [MeshHandle, _pp]),
+    "kde_mesh_counts_device": (_i, [MeshHandle, _pp]),
+    "kde_mesh_tri_counts_device": (_i, [MeshHandle, _pp]),
+    "kde_mesh_counts_host": (_i, [MeshHandle, _vp, _pp]),
+    "kde_mesh_tri_counts_host": (_i, [MeshHandle, _vp, _pp]),
+    "kde_mesh_vertices_host": (_i, [MeshHandle, _vp, _pp, _pp]),
+    "kde_mesh_triangles_host": (_i, [MeshHandle, _vp, _pp, _pp]),
     "kde_reg_default_params": (_i, [C.POINTER(RegParams)]),
     "kde_reg_create": (_i, [C.POINTER(RegHandle), _i, _i, _i, _i, _i, C.POINTER(RegParams)]),
     "kde_reg_destroy": (_i, [RegHandle]),

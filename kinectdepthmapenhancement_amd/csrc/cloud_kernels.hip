@@ -205,6 +205,14 @@ __global__ __launch_bounds__(kThreads) void cloud_write_kernel(CloudLaunch a)
 
 }  // namespace
 
+// C2 on its own, for another table of per-segment counts (mesh_kernels.hip): offsets in place, the totals of the n frames
+int launch_segment_scan(uint32_t* seg, unsigned segs, uint32_t* counts, int n, hipStream_t s)
+{
+    hipLaunchKernelGGL(cloud_scan_kernel, dim3((unsigned)n), dim3(kCloudScanThreads), 0, s, seg, segs, counts);
+    KDE_HIP_TRY(hipGetLastError());
+    return KDE_OK;
+}
+
 int launch_cloud(const CloudLaunch& a, hipStream_t s)
 {
     const size_t px = (size_t)a.cam.width * a.cam.height;

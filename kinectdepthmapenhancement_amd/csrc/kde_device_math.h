@@ -31,6 +31,23 @@ __device__ __forceinline__ void store_depth(char* frame, bool is_f32, size_t at,
     else reinterpret_cast<uint16_t*>(frame)[at] = depth_to_u16(z);
 }
 
+// ---- the depth link of DepthSpeckleFilter and OrganizedMesh (speckle_kernels.hip, mesh_kernels.hip) ------------------------
+// |za - zb| <= max_diff + rel_diff * min(za, zb) for two depths that are both valid: one subtraction, one product, one sum,
+// each rounded on its own (-ffp-contract=off)
+__device__ __forceinline__ bool depth_close(float za, float zb, float max_diff, float rel_diff)
+{
+    const float m = rel_diff * fminf(za, zb);
+    const float t = max_diff + m;
+    return fabsf(za - zb) <= t;
+}
+
+// the link of the speckle rule: a state of 0 is an invalid pixel and links to nothing
+__device__ __forceinline__ bool linked(float za, float zb, float max_diff, float rel_diff)
+{
+    if (!(za > 0.0f && zb > 0.0f)) return false;
+    return depth_close(za, zb, max_diff, rel_diff);
+}
+
 // a packed BGR pixel as b | g << 8 | r << 16: |db| + |dg| + |dr| of two of them is one v_sad_u8
 __device__ __forceinline__ uint32_t pack_bgr(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16); }
 

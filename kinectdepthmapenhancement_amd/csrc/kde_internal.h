@@ -232,6 +232,25 @@ struct CloudLaunch {
     kde_cloud_point* out;                          // [n][H][W] records, 16-byte aligned: frame f's slot starts at f * W * H
 };
 int launch_cloud(const CloudLaunch& a, hipStream_t s);
+// C2 alone: seg [n][segs] counts become offsets in place, counts[f] the total of frame f
+int launch_segment_scan(uint32_t* seg, unsigned segs, uint32_t* counts, int n, hipStream_t s);
+
+// OrganizedMesh (mesh_kernels.hip): the triangles of the depth grid over the dense cloud of launch_cloud.  The tables are
+// per frame and cover whole segments of kCloudSegmentPixels pixels: a pixel beyond the frame is an invalid pixel without a quad.
+constexpr unsigned kMeshGroupPixels = 64;          // pixels one validity word and one rank prefix stand for
+inline size_t mesh_table_pixels(size_t frame_px) { return (size_t)cloud_segments(frame_px) * kCloudSegmentPixels; }
+struct MeshLaunch {
+    CloudLaunch cloud;                             // the vertices: dense mode; seg holds the segments' vertex offsets after it ran
+    float max_diff, rel_diff;
+    int diagonal, flip_winding;
+    uint8_t* mask;                                 // [n][table pixels / 8]: bit k of byte t = pixel 8 t + k is a vertex
+    uint32_t* group_rank;                          // [n][table pixels / 64]: vertices of the segment before the group
+    uint8_t* code;                                 // [n][table pixels]: the triangles the pixel's quad gives, a set of four forms
+    uint32_t* tri_seg;                             // [n][segments]: triangle counts after M1, offsets after M2
+    uint32_t* tri_counts;                          // [n]
+    kde_mesh_triangle* triangles;                  // [n][2 (W-1) (H-1)] records, 4-byte aligned
+};
+int launch_mesh(const MeshLaunch& a, hipStream_t s);
 
 // DepthRegistration (reg_kernels.hip): what Kinect.cpp:71-75 asks OpenNI for -- the depth map as the colour camera sees it
 struct RegCalib {

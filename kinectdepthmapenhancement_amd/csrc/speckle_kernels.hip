@@ -71,15 +71,6 @@ __device__ __forceinline__ Frame frame_of(const SpeckleLaunch& L, unsigned frame
     return Frame{static_cast<const char*>(L.depth) + (size_t)frame * px * (f32 ? sizeof(float) : sizeof(uint16_t)), f32, L.z_min, L.z_max};
 }
 
-// the link of the rule: one subtraction, one product, one sum, each rounded on its own (-ffp-contract=off)
-__device__ __forceinline__ bool linked(float za, float zb, float max_diff, float rel_diff)
-{
-    if (!(za > 0.0f && zb > 0.0f)) return false;
-    const float m = rel_diff * fminf(za, zb);
-    const float t = max_diff + m;
-    return fabsf(za - zb) <= t;
-}
-
 // S1: grid (tiles of a frame, n), block 256
 template <bool CONN8>
 __global__ __launch_bounds__(kThreads) void speckle_tile_kernel(SpeckleLaunch L)

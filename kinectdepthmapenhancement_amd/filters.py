@@ -968,6 +968,116 @@ class PointCloudXYZRGB(_Handle):
         return [raw[int(offsets[f]):int(offsets[f + 1])] for f in range(self._n)]
 
 
+class OrganizedMesh(_Handle):
+    """The surface of main.cpp:211-300 as a triangle mesh of the organised grid (kde_mesh_*), for up to `max_batch` frames in
+    one call.  A source is what PointCloudXYZRGB takes.  The vertices are exactly that class's dense cloud (the same bytes);
+    the vertex index of a valid pixel is its rank in raster order.  Pixel (x, y), x < W-1, y < H-1, owns the quad a = (x, y),
+    b = (x+1, y), c = (x, y+1), d = (x+1, y+1); a triangle is emitted iff its corners are valid and its edges linked,
+    |za - zb| <= max_diff + rel_diff * min(za, zb) on the source's z in millimetres.  Four valid corners are cut along a-d
+    (diagonal = DIAG_AD), b-c (DIAG_BC) or the shorter of the two in z (DIAG_ADAPTIVE, the default; a tie goes to a-d); three
+    valid corners give their one triangle.  Triangles are 12-byte records of three uint32, ordered by owning pixel, the first
+    tri_counts()[f] records of frame f's slot of 2 (W-1) (H-1); nothing is written behind them."""
+    _destroy = "kde_mesh_destroy"
+    _handle_type = _native.MeshHandle
+    POINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("rgb", "<u4")])
+    TRIANGLE_DTYPE = np.dtype([("v0", "<u4"), ("v1", "<u4"), ("v2", "<u4")])
+    DIAG_AD, DIAG_BC, DIAG_ADAPTIVE = _native.KDE_MESH_DIAG_AD, _native.KDE_MESH_DIAG_BC, _native.KDE_MESH_DIAG_ADAPTIVE
+
+    def __init__(self, width: int, height: int, max_batch: int = 1, z_min: float = 50.0, z_max: float = 15000.0,
+                 divisor: float = 1000.0, negate_z: bool = True, max_diff: float = 10.0, rel_diff: float = 0.02,
+                 diagonal: int = _native.KDE_MESH_DIAG_ADAPTIVE, flip_winding: bool = False):
+        super().__init__()
+        self.width, self.height, self.max_batch = width, height, max_batch
+        self.tri_slot = 2 * (width - 1) * (height - 1)
+        self._n = 0
+        p = _native.MeshParams(z_min, z_max, divisor, int(bool(negate_z)), max_diff, rel_diff, int(diagonal), int(bool(flip_winding)))
+        check(lib().kde_mesh_create(C.byref(self._h), width, height, max_batch, C.byref(p)))
+
+    @staticmethod
+    def default_params() -> "_native.MeshParams":
+        p = _native.MeshParams()
+        check(lib().kde_mesh_default_params(C.byref(p)))
+        return p
+
+    def set_camera(self, K) -> None:
+        k = _K9(K)
+        check(lib().kde_mesh_set_camera(self._h, k.ctypes.data))
+
+    def build(self, source: torch.Tensor, bgr: torch.Tensor, vertices_out: Optional[torch.Tensor] = None,
+              triangles_out: Optional[torch.Tensor] = None) -> None:
+        """source: n frames; bgr: uint8 [n,H,W,3] or [1,H,W,3]; vertices_out: uint8 [n, H*W, 16], triangles_out: uint8
+        [n, 2(W-1)(H-1), 12] (on a 4-byte boundary), or None for the object-owned buffers.  Asynchronous on torch's current
+        stream; no allocation, copy or synchronisation on the device."""
+        src, n = _source_of(self.width, self.height, source, "source")
+        if not isinstance(bgr, torch.Tensor) or bgr.dim() != 4 or bgr.shape[0] not in (1, n):
+            raise ValueError(f"bgr: expected [1 or {n},{self.height},{self.width},3] uint8")
+        _req(bgr, torch.uint8, (bgr.shape[0], self.height, self.width, 3), "bgr")
+        if vertices_out is not None:
+            _req(vertices_out, torch.uint8, (n, self.height * self.width, 16), "vertices_out")
+        if triangles_out is not None:
+            _req(triangles_out, torch.uint8, (n, self.tri_slot, 12), "triangles_out")
+        check(lib().kde_mesh_build_batch(self._h, n, C.byref(src), bgr.data_ptr(), bgr.shape[0], _ptr(vertices_out),
+                                         _ptr(triangles_out), _stream()))
+        self._n = n
+
+    def _u32_host(self, name: str) -> np.ndarray:
+        p = C.c_void_p()
+        check(getattr(lib(), name)(self._h, _stream(), C.byref(p)))
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint32)), shape=(self._n,)).copy()
+
+    def counts(self) -> np.ndarray:
+        """the number of vertices per frame of the last build, uint32 [n]; synchronises torch's current stream"""
+        return self._u32_host("kde_mesh_counts_host")
+
+    def tri_counts(self) -> np.ndarray:
+        """the number of triangles per frame of the last build, uint32 [n]; synchronises torch's current stream"""
+        return self._u32_host("kde_mesh_tri_counts_host")
+
+    def _device(self, name: str, shape) -> torch.Tensor:
+        p = C.c_void_p()
+        check(getattr(lib(), name)(self._h, C.byref(p)))
+        return _view(p.value, shape, torch.uint8, self)
+
+    def counts_device(self) -> torch.Tensor:
+        """counts() on the device, as raw bytes [n, 4] (uint32), a view of the object-owned buffer"""
+        return self._device("kde_mesh_counts_device", (self._n, 4))
+
+    def tri_counts_device(self) -> torch.Tensor:
+        """tri_counts() on the device, as raw bytes [n, 4] (uint32), a view of the object-owned buffer"""
+        return self._device("kde_mesh_tri_counts_device", (self._n, 4))
+
+    def vertices_device(self) -> torch.Tensor:
+        """the vertex records of the last build as raw bytes [n, H*W, 16] (POINT_DTYPE); only the first counts()[f] of frame f
+        are defined"""
+        return self._device("kde_mesh_vertices_device", (self._n, self.height * self.width, 16))
+
+    def triangles_device(self) -> torch.Tensor:
+        """the triangle records of the last build as raw bytes [n, 2(W-1)(H-1), 12] (TRIANGLE_DTYPE); only the first
+        tri_counts()[f] of frame f are defined"""
+        return self._device("kde_mesh_triangles_device", (self._n, self.tri_slot, 12))
+
+    def _packed_host(self, name: str, dtype) -> tuple:
+        p, off = C.c_void_p(), C.c_void_p()
+        check(getattr(lib(), name)(self._h, _stream(), C.byref(p), C.byref(off)))
+        offsets = np.ctypeslib.as_array(C.cast(off, C.POINTER(C.c_uint64)), shape=(self._n + 1,)).copy()
+        total = int(offsets[-1])
+        if total == 0:
+            return [np.empty(0, dtype) for _ in range(self._n)], offsets
+        raw = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(total * dtype.itemsize,)).copy().view(dtype)
+        return [raw[int(offsets[f]):int(offsets[f + 1])] for f in range(self._n)], offsets
+
+    def vertices_host(self) -> list:
+        """one structured array (POINT_DTYPE) of counts()[f] records per frame (offsets in self.offsets); synchronises"""
+        frames, self.offsets = self._packed_host("kde_mesh_vertices_host", self.POINT_DTYPE)
+        return frames
+
+    def triangles_host(self) -> list:
+        """one structured array (TRIANGLE_DTYPE) of tri_counts()[f] records per frame (offsets in self.tri_offsets);
+        synchronises"""
+        frames, self.tri_offsets = self._packed_host("kde_mesh_triangles_host", self.TRIANGLE_DTYPE)
+        return frames
+
+
 class _DepthStage(_Handle):
     """What the depth-in / depth-out stages share (csrc/kde_depth_stage.h in the library): n depth frames in as float32 or
     uint16, n frames out in either format, the results of the last batch call.  A subclass names its C prefix and its
