@@ -41,7 +41,7 @@ int kde_test_tree256(const int32_t* iv_rows_dev, const float* fv_rows_dev, uint3
 
 /* ---- tools/hooks/libkde_hip_stage.so ------------------------------------------------------------------------------
  * The product library's own sources compiled with -DKDE_STAGE_HOOKS: every entry point of include/kde_hip.h (same
- * code, same flags) plus the one below.  It exists so that the parity tests can check K1 and K10 STAGE BY STAGE: the
+ * code, same flags) plus the four below.  It exists so that the parity tests can check K1 and K10 STAGE BY STAGE: the
  * composite filters are ill-conditioned only through their first-pass average (and K10's deviation), each stage by
  * itself is well-conditioned, so the tests take the GPU's own average / deviation, re-evaluate the last pass from
  * them in binary64 on the CPU and hold the GPU's final value to 1e-4 against that (oracle/oracle.py: stage_check_*).
@@ -77,6 +77,34 @@ struct kde_spdsr;
 struct kde_float3;
 int kde_stage_spdsr_tail(struct kde_spdsr* h, int n, const int32_t* labels_dev, const struct kde_float3* points_dev,
                          const float* nd_dev_or_null, int sweeps, void* stream);
+
+/* ---- the size-selected kernel forms --------------------------------------------------------------------------------
+ * Twelve launch sites of the library (csrc/kde_internal.h: CacheSite, past_cache) pick the streaming twin of their kernel
+ * -- non-temporal loads and stores, nothing else differs -- when a call moves more than 256 MiB.  The stage build lets a
+ * test reach the twin at any shape and proves that it did:
+ *
+ * kde_stage_set_cache_bytes(bytes) — process-wide, applies to later calls: the sites compare with `bytes` instead of
+ *   256 MiB.  0: every call streams (where the site's other conditions, such as 16-byte alignment, hold).
+ *   (size_t)256 << 20 restores the product's behaviour.
+ * kde_stage_streaming_launches(counts, n) — copies out the first n (0 .. KDE_STAGE_SITES) host counters and zeroes all of
+ *   them.  counts[site] = how often that site has launched its streaming form since the last call.  Not thread-safe. */
+enum kde_stage_site {
+    KDE_STAGE_SITE_P2R_DEPTH = 0,        /* kde_dimconv_projective_to_real_depth / _interp: vector form only */
+    KDE_STAGE_SITE_POINTS_MAP,           /* kde_dimconv_projective_to_real_points / real_to_projective: vector form only */
+    KDE_STAGE_SITE_POINTS_TO_DEPTH_F32,  /* kde_points_to_depth, float output: vector form only */
+    KDE_STAGE_SITE_POINTS_TO_DEPTH_U16,  /* kde_points_to_depth, uint16 output: vector form only */
+    KDE_STAGE_SITE_CLOUD,                /* kde_cloud_build_batch, and the vertices of kde_mesh_build_batch */
+    KDE_STAGE_SITE_MESH,                 /* kde_mesh_build_batch: classify and emit */
+    KDE_STAGE_SITE_ERROR3D,              /* kde_error3d_compare_batch */
+    KDE_STAGE_SITE_UNDIST_COLOR,         /* kde_undist_color_batch */
+    KDE_STAGE_SITE_UNDIST_DEPTH,         /* kde_undist_depth_batch */
+    KDE_STAGE_SITE_REG,                  /* kde_reg_register_batch: scatter and finalise */
+    KDE_STAGE_SITE_REG_GATHER,           /* kde_reg_color_to_depth_batch */
+    KDE_STAGE_SITE_TEMPORAL,             /* kde_temporal_filter_batch */
+    KDE_STAGE_SITES
+};
+int kde_stage_set_cache_bytes(size_t bytes);
+int kde_stage_streaming_launches(uint64_t* counts, int n);
 
 #ifdef __cplusplus
 }

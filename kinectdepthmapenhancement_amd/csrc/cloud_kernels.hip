@@ -219,7 +219,7 @@ int launch_cloud(const CloudLaunch& a, hipStream_t s)
     const unsigned segs = cloud_segments(px);
     const size_t esz = a.format == KDE_SRC_POINTS_F32 ? sizeof(kde_float3) : a.format == KDE_SRC_DEPTH_F32 ? sizeof(float) : sizeof(uint16_t);
     const size_t bytes = px * a.n * (esz + sizeof(kde_cloud_point)) + px * a.bgr_frames * 3;
-    const bool nt = bytes > kCacheBytes;
+    const bool nt = past_cache(kSiteCloud, bytes);
     const dim3 grid(segs, (unsigned)a.n), block(kThreads);
     if (a.organized) {
         KDE_HIP_TRY(hipMemsetAsync(a.counts, 0, (size_t)a.n * sizeof(uint32_t), s));

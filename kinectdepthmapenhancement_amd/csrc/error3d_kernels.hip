@@ -139,7 +139,7 @@ int launch_error3d(const Error3dLaunch& a, hipStream_t s)
     size_t bytes = px * a.truth_frames * esz(a.truth_format);
     for (int c = 0; c < a.m; c++) bytes += px * a.n * esz(a.cand_format[c]);
     const dim3 grid(segs, (unsigned)a.n), block(kThreads);
-    if (bytes > kCacheBytes) hipLaunchKernelGGL(error3d_partial_kernel<true>, grid, block, 0, s, a);
+    if (past_cache(kSiteError3d, bytes)) hipLaunchKernelGGL(error3d_partial_kernel<true>, grid, block, 0, s, a);
     else hipLaunchKernelGGL(error3d_partial_kernel<false>, grid, block, 0, s, a);
     hipLaunchKernelGGL(error3d_final_kernel, dim3((unsigned)(a.n * a.m)), dim3(64), 0, s, a.partials, segs, a.results);
     KDE_HIP_TRY(hipGetLastError());

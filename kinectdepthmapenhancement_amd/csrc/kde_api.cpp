@@ -21,6 +21,8 @@ int fail(int code, const char* fmt, ...)
 
 #ifdef KDE_STAGE_HOOKS
 StageCtl g_stage = {nullptr, nullptr, nullptr, nullptr, 0};
+size_t g_stage_cache_bytes = kCacheBytes;
+uint64_t g_stage_streaming[kCacheSites] = {};
 #endif
 
 }  // namespace kde
@@ -36,6 +38,21 @@ extern "C" int kde_stage_set(float* jbf_avg_dev, float* ers_avg_dev, float* ers_
     g_stage.ers_dev = ers_dev_dev;
     g_stage.counters = counters_dev;
     g_stage.force_full_rules = force_full_rules;
+    return KDE_OK;
+}
+
+extern "C" int kde_stage_set_cache_bytes(size_t bytes)
+{
+    g_stage_cache_bytes = bytes;
+    return KDE_OK;
+}
+
+extern "C" int kde_stage_streaming_launches(uint64_t* counts, int n)
+{
+    KDE_REQUIRE(n >= 0 && n <= (int)kCacheSites && (counts || n == 0), "kde_stage_streaming_launches: n=%d outside 0..%d, or null counts",
+                n, (int)kCacheSites);
+    for (int i = 0; i < n; i++) counts[i] = g_stage_streaming[i];
+    std::fill(g_stage_streaming, g_stage_streaming + kCacheSites, (uint64_t)0);
     return KDE_OK;
 }
 #endif

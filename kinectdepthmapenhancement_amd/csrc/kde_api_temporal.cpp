@@ -122,7 +122,7 @@ extern "C" int kde_temporal_filter_batch(kde_temporal* h, int n, const void* dep
     a.bgr = bgr_dev;
     a.out = w;
     a.out_format = out_format;
-    a.nt_store = in_bytes + out_bytes + (bgr_dev ? all * 3 : 0) > kCacheBytes;
+    a.nt_store = past_cache(kSiteTemporal, in_bytes + out_bytes + (bgr_dev ? all * 3 : 0));
     a.value = h->value.p;
     a.hist = h->hist.p;
     a.partial = h->partial.p;

@@ -59,6 +59,38 @@ extern StageCtl g_stage;
 #endif
 
 constexpr size_t kCacheBytes = (size_t)256 << 20;   // Infinity Cache: calls that move more than this stream past it (ld4 / st4)
+// The launch sites that pick the streaming twin of their kernel (non-temporal loads / stores) by the bytes a call moves; the
+// order is that of kde_stage_streaming_launches (include/kde_test_hooks.h, tools/hooks/stage.py: SITES)
+enum CacheSite {
+    kSiteP2rDepth,         // stream_kernels.hip launch_p2r_any: p2r_depth_kernel<true> (depth and interp)
+    kSitePointsMap,        // stream_kernels.hip launch_points_any: points_map_kernel<true> (p2r points and r2p)
+    kSitePointsToDepthF32, // stream_kernels.hip launch_points_to_depth: points_to_depth_kernel<true, false>
+    kSitePointsToDepthU16, //                                            points_to_depth_kernel<true, true>
+    kSiteCloud,            // cloud_kernels.hip launch_cloud
+    kSiteMesh,             // mesh_kernels.hip launch_mesh (its launch_cloud counts as kSiteCloud)
+    kSiteError3d,          // error3d_kernels.hip launch_error3d
+    kSiteUndistColor,      // undist_kernels.hip launch_undist_color
+    kSiteUndistDepth,      // undist_kernels.hip launch_undist_depth
+    kSiteReg,              // reg_kernels.hip launch_reg
+    kSiteRegGather,        // reg_kernels.hip launch_reg_gather
+    kSiteTemporal,         // kde_api_temporal.cpp kde_temporal_filter_batch: TemporalLaunch::nt_store
+    kCacheSites
+};
+// Does a call that moves `bytes` stream past the cache?  The one statement of the decision for every site above: a site asks
+// exactly when the answer `true` makes it launch its streaming form.  The stage build compares with a threshold a test can
+// set (kde_stage_set_cache_bytes) and counts the answers `true` per site; the product library has the constant and no state.
+#ifdef KDE_STAGE_HOOKS
+extern size_t g_stage_cache_bytes;
+extern uint64_t g_stage_streaming[kCacheSites];
+inline bool past_cache(CacheSite site, size_t bytes)
+{
+    const bool yes = bytes > g_stage_cache_bytes;
+    if (yes) g_stage_streaming[site]++;
+    return yes;
+}
+#else
+inline bool past_cache(CacheSite, size_t bytes) { return bytes > kCacheBytes; }
+#endif
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 

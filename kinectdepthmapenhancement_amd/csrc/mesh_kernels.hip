@@ -207,7 +207,7 @@ int launch_mesh(const MeshLaunch& a, hipStream_t s)
     const size_t esz = c.format == KDE_SRC_POINTS_F32 ? sizeof(kde_float3) : c.format == KDE_SRC_DEPTH_F32 ? sizeof(float) : sizeof(uint16_t);
     const size_t slot = 2 * (size_t)(c.cam.width - 1) * (c.cam.height - 1);
     const size_t bytes = px * c.n * (esz + sizeof(kde_cloud_point)) + px * c.bgr_frames * 3 + slot * c.n * sizeof(kde_mesh_triangle);
-    const bool nt = bytes > kCacheBytes;
+    const bool nt = past_cache(kSiteMesh, bytes);
     const dim3 grid(segs, (unsigned)c.n), block(kThreads);
     if (nt) hipLaunchKernelGGL(mesh_classify_kernel<true>, grid, block, 0, s, a);
     else hipLaunchKernelGGL(mesh_classify_kernel<false>, grid, block, 0, s, a);

@@ -314,7 +314,7 @@ __global__ __launch_bounds__(kThreads) void reg_gather_kernel(RegLaunch L, const
 int launch_reg(const RegLaunch& a, hipStream_t s)
 {
     const size_t pxd = (size_t)a.wd * a.hd, pxc = (size_t)a.wc * a.hc;
-    const bool nt = (size_t)a.n * (pxd * depth_element(a.depth_format) + pxc * depth_element(a.out_format)) > kCacheBytes;
+    const bool nt = past_cache(kSiteReg, (size_t)a.n * (pxd * depth_element(a.depth_format) + pxc * depth_element(a.out_format)));
     const dim3 block(kThreads);
     const dim3 sgrid((unsigned)((pxd + kBlockPixels - 1) / kBlockPixels), (unsigned)a.n);
     const dim3 fgrid((unsigned)((pxc + kThreads * kOctet - 1) / (kThreads * kOctet)), (unsigned)a.n);
@@ -333,7 +333,7 @@ int launch_reg(const RegLaunch& a, hipStream_t s)
 int launch_reg_gather(const RegLaunch& a, const uint8_t* bgr, int bgr_frames, uint8_t* out, hipStream_t s)
 {
     const size_t pxd = (size_t)a.wd * a.hd, pxc = (size_t)a.wc * a.hc;
-    const bool nt = (size_t)a.n * pxd * (depth_element(a.depth_format) + 3) + (size_t)bgr_frames * pxc * 3 > kCacheBytes;
+    const bool nt = past_cache(kSiteRegGather, (size_t)a.n * pxd * (depth_element(a.depth_format) + 3) + (size_t)bgr_frames * pxc * 3);
     const dim3 grid((unsigned)((pxd + kBlockPixels - 1) / kBlockPixels), (unsigned)a.n), block(kThreads);
     if (nt) hipLaunchKernelGGL(reg_gather_kernel<true>, grid, block, 0, s, a, bgr, bgr_frames, out);
     else hipLaunchKernelGGL(reg_gather_kernel<false>, grid, block, 0, s, a, bgr, bgr_frames, out);

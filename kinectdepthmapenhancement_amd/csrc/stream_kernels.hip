@@ -441,8 +441,7 @@ static bool p2r_vector_ok(const Camera& c, int n, const void* in, const void* ou
 static int launch_p2r_any(const Camera& c, int n, const float* depth, kde_float3* out, int interp, hipStream_t s)
 {
     const size_t frame_px = (size_t)c.width * c.height;
-    const bool streaming = frame_px * n * 16 > kCacheBytes;
-    if (p2r_vector_ok(c, n, depth, out) && streaming)
+    if (p2r_vector_ok(c, n, depth, out) && past_cache(kSiteP2rDepth, frame_px * n * 16))
         hipLaunchKernelGGL(p2r_depth_kernel<true>, dim3(grid_for(frame_px / 4 + 1), n), dim3(kThreads), 0, s, c, depth,
                            reinterpret_cast<float*>(out), interp);
     else if (p2r_vector_ok(c, n, depth, out))
@@ -468,8 +467,7 @@ int launch_p2r_interp(const Camera& c, int n, const float* depth, kde_float3* ou
 static int launch_points_any(const Camera& c, int n, const kde_float3* in, kde_float3* out, int to_projective, hipStream_t s)
 {
     const size_t total = (size_t)c.width * c.height * n;
-    const bool streaming = total * 24 > kCacheBytes;
-    if (aligned(in, 16) && aligned(out, 16) && streaming)
+    if (aligned(in, 16) && aligned(out, 16) && past_cache(kSitePointsMap, total * 24))
         hipLaunchKernelGGL(points_map_kernel<true>, dim3(grid_for(total / 4 + 1)), dim3(kThreads), 0, s, c, total,
                            reinterpret_cast<const float*>(in), reinterpret_cast<float*>(out), to_projective);
     else if (aligned(in, 16) && aligned(out, 16))
@@ -568,8 +566,8 @@ int launch_points_to_depth(const kde_float3* pts, void* out, size_t n, bool u16,
     // vector form: whole groups of 8 points when both pointers are 16-byte aligned; the last n % 8 points, or everything
     // otherwise, go through the scalar form
     const size_t groups = aligned(pts, 16) && aligned(out, 16) ? n / 8 : 0;
-    const bool streaming = n * (12 + (u16 ? 2 : 4)) > kCacheBytes;
     if (groups) {
+        const bool streaming = past_cache(u16 ? kSitePointsToDepthU16 : kSitePointsToDepthF32, n * (12 + (u16 ? 2 : 4)));
         const dim3 grid(grid_for(groups)), block(kThreads);
         if (u16 && streaming) hipLaunchKernelGGL((points_to_depth_kernel<true, true>), grid, block, 0, s, groups, in, out);
         else if (u16) hipLaunchKernelGGL((points_to_depth_kernel<false, true>), grid, block, 0, s, groups, in, out);

@@ -314,7 +314,7 @@ __global__ __launch_bounds__(kThreads) void undist_map_kernel(UndistCalib c, uns
 int launch_undist_color(const UndistLaunch& a, const uint8_t* bgr, int bgr_frames, uint8_t* out, hipStream_t s)
 {
     const size_t spx = (size_t)a.sw * a.sh, opx = (size_t)a.ow * a.oh;
-    const bool nt = ((size_t)bgr_frames * spx + (size_t)a.n * opx) * 3 > kCacheBytes;
+    const bool nt = past_cache(kSiteUndistColor, ((size_t)bgr_frames * spx + (size_t)a.n * opx) * 3);
     const dim3 grid((unsigned)((opx + kBlockPixels - 1) / kBlockPixels), (unsigned)a.n), block(kThreads);
     if (nt) hipLaunchKernelGGL(undist_color_kernel<true>, grid, block, 0, s, a, bgr, bgr_frames, out);
     else hipLaunchKernelGGL(undist_color_kernel<false>, grid, block, 0, s, a, bgr, bgr_frames, out);
@@ -325,7 +325,7 @@ int launch_undist_color(const UndistLaunch& a, const uint8_t* bgr, int bgr_frame
 int launch_undist_depth(const UndistLaunch& a, hipStream_t s)
 {
     const size_t spx = (size_t)a.sw * a.sh, opx = (size_t)a.ow * a.oh;
-    const bool nt = (size_t)a.n * (spx * depth_element(a.depth_format) + opx * depth_element(a.out_format)) > kCacheBytes;
+    const bool nt = past_cache(kSiteUndistDepth, (size_t)a.n * (spx * depth_element(a.depth_format) + opx * depth_element(a.out_format)));
     const size_t per_block = (size_t)kBlockPixels * kDepthTiles;
     const dim3 grid((unsigned)((opx + per_block - 1) / per_block), (unsigned)a.n), block(kThreads);
     hipLaunchKernelGGL(undist_reset_kernel, dim3((unsigned)((a.n + kThreads - 1) / kThreads)), block, 0, s, a.filled, (unsigned)a.n);

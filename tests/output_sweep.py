@@ -30,8 +30,10 @@ The bars, none new:
   cloud     test_gpu_cloud.py: the bytes of cloud_cases.statement, exact counts, nothing written behind count[f]
   error3d   test_gpu_error3d.py: exact counts, the sum within count * 2^-53 * sum of the exact sum of the float32 terms, the
             mean as the float conversion of sum / count
-tests/test_output_sweep.py holds the conditions on the draw.  The non-temporal forms of K2/K3 start at calls that move more
-than 256 MB, far beyond the frames drawn here: the sweep reaches the vector and the scalar forms only.
+tests/test_output_sweep.py holds the conditions on the draw.  The non-temporal forms of K2/K3, the cloud and the metric start
+at calls that move more than 256 MiB, far beyond the frames drawn here: tests/test_gpu_output_sweep.py reaches the vector and
+the scalar forms only, tests/test_gpu_streaming_forms.py runs the same cases again on the stage build with the threshold at 0
+(convert_streaming_sites says which `convert` cases then stream).
 
 This module needs no GPU: torch and the filters module are handed to run_case().
 """
@@ -289,6 +291,24 @@ def depth_stack_case():
     c.depth = (1000.0 + 10.0 * np.arange(27)).astype(F).reshape(3, 3, 3)
     c.points = np.stack([c.depth * F(0.5), c.depth * F(-0.25), c.depth], -1).astype(F)
     return c
+
+
+def convert_streaming_sites(c):
+    """the launch sites of csrc/stream_kernels.hip whose streaming form a `convert` case reaches once the cache threshold is 0
+    (tools/hooks/stage.py: set_cache_bytes), as _run_convert places its tensors: the streaming forms are vector forms.
+    launch_p2r_any wants depth and out on 16-byte boundaries and, with more than one frame, W * H % 4 == 0; launch_points_any
+    wants its two clouds there (r2p_chain goes from `out` to `out`); points_to_depth wants the cloud and its map there and
+    at least one group of 8 points"""
+    (W, H), o = c.size, c.off
+    sites = set()
+    if o["depth"] == 0 and o["out"] == 0 and (c.n == 1 or W * H % 4 == 0):
+        sites.add("p2r_depth")
+    if o["out"] == 0:
+        sites.add("points_map")
+    for key, site in (("zf", "points_to_depth_f32"), ("zu", "points_to_depth_u16")):
+        if o["points"] == 0 and o[key] == 0 and c.n * W * H >= 8:
+            sites.add(site)
+    return sites
 
 
 def _f3(p):

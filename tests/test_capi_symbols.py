@@ -50,20 +50,50 @@ def test_hooks_are_not_part_of_the_product_abi(native):
     assert {n for n in exported if n.startswith("kde_")} == set(declared_functions())
 
 
-def test_stage_build_is_the_same_abi_plus_two_hooks(native):
+STAGE_HOOKS = ("kde_stage_set", "kde_stage_spdsr_tail", "kde_stage_set_cache_bytes", "kde_stage_streaming_launches")
+
+
+def test_stage_build_is_the_same_abi_plus_four_hooks(native):
     """tools/hooks/libkde_hip_stage.so = the product sources with -DKDE_STAGE_HOOKS: every product symbol plus
-    kde_stage_set and kde_stage_spdsr_tail (include/kde_test_hooks.h), which the product library must not contain"""
+    kde_stage_set, kde_stage_spdsr_tail, kde_stage_set_cache_bytes and kde_stage_streaming_launches
+    (include/kde_test_hooks.h), which the product library must not contain"""
     path = os.path.join(ROOT, "tools", "hooks", "libkde_hip_stage.so")
     subprocess.check_call(["make", "-C", os.path.dirname(path), "-s", "-j8", "libkde_hip_stage.so"])     # no-op when up to date
     out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True).stdout
     exported = {ln.split()[-1] for ln in out.splitlines() if " T " in ln and ln.split()[-1].startswith("kde_")}
-    assert exported == set(declared_functions()) | {"kde_stage_set", "kde_stage_spdsr_tail"}
+    assert exported == set(declared_functions()) | set(STAGE_HOOKS)
     hooks_header = open(os.path.join(ROOT, "include", "kde_test_hooks.h")).read()
     prod = subprocess.run(["nm", "-D", "--defined-only", native.LIB_PATH], capture_output=True, text=True).stdout
-    for hook in ("kde_stage_set", "kde_stage_spdsr_tail"):
-        assert hook in hooks_header and hook not in open(HEADER).read()
+    for hook in STAGE_HOOKS:
+        assert re.search(r"\bint %s\(" % hook, hooks_header) and hook not in open(HEADER).read()
         assert hook not in prod
     assert "g_stage" not in prod
+    # no state of the hooks in the product library, among all its symbols: the threshold there is a constant
+    assert "g_stage" not in subprocess.run(["nm", "-C", native.LIB_PATH], capture_output=True, text=True).stdout
+
+
+def test_stage_sites_are_named_alike_in_the_three_places(native):
+    """enum CacheSite (csrc/kde_internal.h), enum kde_stage_site (include/kde_test_hooks.h) and stage.SITES in one order; the
+    counters are host state: read, zeroed and refused without a device"""
+    from tools.hooks import stage
+    internal = open(os.path.join(native.CSRC, "kde_internal.h")).read()
+    body = re.search(r"enum CacheSite \{(.*?)\};", internal, re.S).group(1)
+    csite = [re.sub(r"(?<!^)(?=[A-Z0-9])", "_", n[5:]).lower() for n in re.findall(r"^\s*(kSite\w+),", body, re.M)]
+    hooks = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "kde_test_hooks.h")).read(), flags=re.S)
+    hsite = [n.lower() for n in re.findall(r"KDE_STAGE_SITE_(\w+)", re.search(r"enum kde_stage_site \{(.*?)\};", hooks, re.S).group(1))]
+    norm = lambda names: [n.replace("_", "") for n in names]
+    assert len(stage.SITES) == 12 and norm(csite) == norm(stage.SITES) == norm(hsite), (csite, hsite, stage.SITES)
+    assert body.count("kCacheSites") == 1 and "KDE_STAGE_SITES" in hooks
+    # every size decision of the library goes through past_cache: the constant is named where it is defined and nowhere else
+    for f in sorted(os.listdir(native.CSRC)):
+        if f.endswith((".hip", ".cpp", ".h")) and f != "kde_internal.h":
+            assert "kCacheBytes" not in re.sub(r"//.*", "", open(os.path.join(native.CSRC, f)).read()) or f == "kde_api.cpp", f
+    l = stage.lib()
+    buf = (ctypes.c_uint64 * 13)(*([7] * 13))
+    assert l.kde_stage_streaming_launches(buf, 12) == 0 and list(buf) == [0] * 12 + [7]
+    assert l.kde_stage_streaming_launches(buf, 13) == native.KDE_ERR_INVALID and l.kde_stage_streaming_launches(None, 1) == native.KDE_ERR_INVALID
+    assert l.kde_stage_streaming_launches(None, 0) == 0
+    assert stage.StageCtl(l).streaming_launches() == dict.fromkeys(stage.SITES, 0)
 
 
 def test_python_binding_covers_the_header(native):

@@ -12,6 +12,8 @@ quad lie one row ahead):
   131 x 67    8777 pixels: five segments, odd rows, frames of a batch alternate between the 16-byte and the element loads
   2049 x 3    a row longer than a segment: c and d rank through the segment two ahead
   640 x 480   150 segments: many workgroups, every table in use
+  1026 x 513  526 338 pixels: 258 segments, the last of 2 pixels.  launch_segment_scan takes 256 segment counts per pass
+              (kCloudScanThreads): the vertex offsets, the triangle offsets and the rank tables come from its second pass
 """
 import numpy as np
 import pytest
@@ -24,6 +26,7 @@ pytestmark = pytest.mark.gpu
 
 SIZES = ((2, 2), (70, 33), (64, 64), (131, 67), (2049, 3), (640, 480))
 SMALL = SIZES[:5]
+MULTI_PASS = (1026, 513)
 IDS = [f"{w}x{h}" for w, h in SIZES]
 MODES = (MC.DIAG_AD, MC.DIAG_BC, MC.DIAG_ADAPTIVE)
 SENTINEL = 0xA5
@@ -232,6 +235,30 @@ def test_object_owned_outputs_and_host_getters(torch_cuda, w, h):
     assert [a.tobytes() for a in M.triangles_host()] == [r.tobytes() for r in want_t[:2]]
     assert [a.tobytes() for a in M.vertices_host()] == [r.tobytes() for r in want_v[:2]]
     M.close()
+
+
+def test_more_segments_than_one_pass_of_the_scan(torch_cuda):
+    """1026 x 513: the per-frame scan of the vertex counts and of the triangle counts carries a total from its first 256
+    segments into the next pass, and the last segment holds 2 pixels.  A noisy and a salted frame in one batch under the three
+    diagonals, against the vectorised statement and the dense cloud (the statement of the six frames takes 0.4 s)"""
+    from kinectdepthmapenhancement_amd import filters as F
+    torch = torch_cuda
+    w, h = MULTI_PASS
+    assert -(-w * h // 2048) == 258 and w * h % 2048 == 2
+    K = CC.camera(w, h)
+    z = np.stack([MC.noisy(w, h, 0), MC.salt(w, h)])
+    g = dict(link={}, names=["noisy0", "salt"], z=z, pts=np.stack([MC.as_points(zz, K) for zz in z]), bgr=CC.bgr_images(7 * w + h, 2, h, w),
+             K=K, want={})
+    src, bgr = dev(torch, g["pts"]), dev(torch, g["bgr"])
+    for mode in MODES:
+        _build_and_check(torch, F, w, h, g, src, bgr, mode, what=("multi-pass", mode)).close()
+    sets = [_want(g, m)[0].tobytes() for m in MODES]
+    assert len(set(sets)) == 3 and all(0 < r.size < 2 * (w - 1) * (h - 1) for m in MODES for r in _want(g, m))
+    # a vertex and a triangle behind the first pass of each scan: the counts of the first 256 segments are smaller than the totals
+    first = 256 * 2048
+    assert all(int(MC.valid_mask(zz).reshape(-1)[:first].sum()) < int(MC.valid_mask(zz).sum()) for zz in z)
+    u16 = dev(torch, z[:1].astype(np.uint16).view(np.int16))                   # the uint16 map of the noisy frame: the element loads
+    _build_and_check(torch, F, w, h, g, u16, bgr[:1], frames=[0], what="multi-pass uint16").close()
 
 
 def test_a_batch_without_a_triangle_writes_nothing(torch_cuda):

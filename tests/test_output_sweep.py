@@ -239,6 +239,22 @@ def test_convert_draw(cases):
     assert np.mean(both) >= 0.8                 # both sides of realToProjective's |z| < 1 rule; a frame of a few pixels may miss one
 
 
+def test_convert_reaches_every_streaming_form_in_every_seed(cases):
+    """tests/test_gpu_streaming_forms.py runs the budget again with the cache threshold at 0 and asks every site of
+    csrc/stream_kernels.hip for a streaming launch per seed.  The streaming forms are vector forms, so only the cases whose
+    tensors lie on 16-byte boundaries reach them: counted here, per seed (seed 1, seed 2): p2r_depth 4, 4 of 32; points_map 18,
+    16; points_to_depth float 11, 9; uint16 14, 10.  The p2r_depth cases hold a batch and a frame with a ragged last quad"""
+    sites = ("p2r_depth", "points_map", "points_to_depth_f32", "points_to_depth_u16")
+    for seed in S.SEEDS:
+        reach = [S.convert_streaming_sites(c) for c in cases["convert"] if c.seed == seed]
+        assert all(r <= set(sites) for r in reach)
+        count = {s: sum(s in r for r in reach) for s in sites}
+        assert count["p2r_depth"] >= 4 and count["points_map"] >= 16 and count["points_to_depth_f32"] >= 9 and count["points_to_depth_u16"] >= 10, (seed, count)
+    p2r = [c for c in cases["convert"] if "p2r_depth" in S.convert_streaming_sites(c)]
+    assert any(c.n > 1 for c in p2r) and any(c.n == 1 and c.size[0] * c.size[1] % 4 for c in p2r)
+    assert all(c.n == 1 or c.size[0] * c.size[1] % 4 == 0 for c in p2r)
+
+
 def test_convert_three_depth_frames_of_3x3():
     c = S.want(S.depth_stack_case())
     assert c.depth.shape == (3, 3, 3) and c.want["p2r_depth"].shape == (3, 3, 3, 3)

@@ -1,5 +1,6 @@
 """Loader of tools/hooks/libkde_hip_stage.so (include/kde_test_hooks.h): the product library's own sources compiled with
--DKDE_STAGE_HOOKS -- same ABI, plus kde_stage_set() and kde_stage_spdsr_tail().  Test infrastructure only.
+-DKDE_STAGE_HOOKS -- same ABI, plus kde_stage_set(), kde_stage_spdsr_tail(), kde_stage_set_cache_bytes() and
+kde_stage_streaming_launches().  Test infrastructure only.
 
     with stage_library() as ctl:          # inside the block kinectdepthmapenhancement_amd.filters talks to the stage build
         ctl.set(jbf_avg=tensor)           # K1 dumps its first-pass average there
@@ -33,8 +34,18 @@ def lib() -> C.CDLL:
         l.kde_stage_set.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         l.kde_stage_spdsr_tail.restype = C.c_int
         l.kde_stage_spdsr_tail.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        l.kde_stage_set_cache_bytes.restype = C.c_int
+        l.kde_stage_set_cache_bytes.argtypes = [C.c_size_t]
+        l.kde_stage_streaming_launches.restype = C.c_int
+        l.kde_stage_streaming_launches.argtypes = [C.POINTER(C.c_uint64), C.c_int]
         _lib = l
     return _lib
+
+
+CACHE_BYTES = 256 << 20         # csrc/kde_internal.h: kCacheBytes
+# enum kde_stage_site (include/kde_test_hooks.h), in its order
+SITES = ("p2r_depth", "points_map", "points_to_depth_f32", "points_to_depth_u16", "cloud", "mesh", "error3d", "undist_color",
+         "undist_depth", "reg", "reg_gather", "temporal")
 
 
 class StageCtl:
@@ -52,8 +63,24 @@ class StageCtl:
         if rc:
             raise RuntimeError(f"kde_stage_set failed ({rc})")
 
+    def set_cache_bytes(self, nbytes=CACHE_BYTES):
+        """the threshold above which a call takes the streaming (non-temporal) twin of its kernels; 0: every call does"""
+        rc = self._l.kde_stage_set_cache_bytes(nbytes)
+        if rc:
+            raise RuntimeError(f"kde_stage_set_cache_bytes failed ({rc})")
+
+    def streaming_launches(self):
+        """{site: launches of its streaming form since the last call}, all of SITES; zeroes the counters"""
+        buf = (C.c_uint64 * len(SITES))()
+        rc = self._l.kde_stage_streaming_launches(buf, len(SITES))
+        if rc:
+            raise RuntimeError(f"kde_stage_streaming_launches failed ({rc})")
+        return dict(zip(SITES, (int(v) for v in buf)))
+
     def clear(self):
         self._l.kde_stage_set(None, None, None, None, 0)
+        self._l.kde_stage_set_cache_bytes(CACHE_BYTES)
+        self._l.kde_stage_streaming_launches(None, 0)
 
 
 @contextlib.contextmanager
